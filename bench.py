@@ -6,6 +6,11 @@ stereo CBR 128 kb/s.  A "step" is one pass of the hot path (psycho-acoustics + p
 quantisation loop -> side-info payload in HBM) over one batch of synthetic streams whose PCM is
 already resident in HBM (BASELINE config[1]: batch = 1024 streams x 60 s per GPU).
 
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the
+result line; --dump-outputs DIR also writes a seeded sample of what the last step computed.  Everything else --
+the oracle check of the timed launch, the CPU baseline, the short runs of other BASELINE configs and the
+end-to-end pipeline -- runs only with --full.
+
 Multi-GPU: streams are independent, so a batch of N x 1024 streams is sharded
 statically, rank r owning the contiguous block lamehip.shard_streams(N * 1024, N, r); there is no
 collective anywhere on the data path and no RCCL.  `python bench.py --gpus N` spawns the N ranks
@@ -98,7 +103,7 @@ SIGNAL = ("SURVEY 8(d) recipe on the device: 8 partials with 5 Hz vibrato, band-
 def _cpu_worker(job):
     """One process of the CPU leg (spawned: no GPU context): encode stream `idx' of the saved PCM
     over and over for about `budget' seconds; returns (audio seconds encoded, elapsed)."""
-    path, idx, sr, brate, vbr_q, abr, budget, kind, vbr_mode = job
+    path, idx, sr, brate, vbr_q, abr, budget, kind, vbr_mode, enc_state = job
     import numpy as np
     sys.path.insert(0, os.path.join(ROOT, "deprecated-lame-mirror_amd"))
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -112,10 +117,8 @@ def _cpu_worker(job):
         def run():
             ref.encode(pcm, sr, brate, vbr_q=vbr_q, abr=abr, vbr_mode=vbr_mode)
     else:
-        import lamehip
         orc = helpers.Oracle()
-        enc = lamehip.Encoder(sr, brate, require_device=False, vbr_q=vbr_q, abr=abr, vbr_mode=vbr_mode)
-        cfg, tab = enc.config(), enc.tables()
+        cfg, tab = encoder_state(enc_state)
 
         def run():
             orc.encode_frames(cfg, tab, pcm)
@@ -177,7 +180,15 @@ def _cpu_model():
     return "unknown"
 
 
-def cpu_baseline(host_pcm, sr, brate, vbr_q=None, abr=None, budget=10.0, vbr_mode=4):
+def encoder_state(enc_state):
+    """(config bytes, tables bytes) of an encoder, taken by the parent -> the ctypes structures the oracle reads.  The
+    spawned checker processes get them this way instead of opening an encoder of their own: lame_init_params
+    initialises the GPU wherever one exists, and these processes must not hold the device open."""
+    from lamehip.types import LhConfig, LhTables
+    return LhConfig.from_buffer_copy(enc_state[0]), LhTables.from_buffer_copy(enc_state[1])
+
+
+def cpu_baseline(host_pcm, sr, brate, enc_state, vbr_q=None, abr=None, budget=10.0, vbr_mode=4):
     """P concurrent encodes, P = physical cores (at most as many as there are saved streams),
     plus one process alone for the per-core figure."""
     import multiprocessing as mp
@@ -194,11 +205,12 @@ def cpu_baseline(host_pcm, sr, brate, vbr_q=None, abr=None, budget=10.0, vbr_mod
     try:
         ctx = mp.get_context("spawn")
         with ctx.Pool(1) as pool:
-            a, t = pool.map(_cpu_worker, [(tmp.name, 0, sr, brate, vbr_q, abr, min(budget, 4.0), kind, vbr_mode)])[0]
+            a, t = pool.map(_cpu_worker, [(tmp.name, 0, sr, brate, vbr_q, abr, min(budget, 4.0), kind, vbr_mode,
+                                           enc_state)])[0]
         single = a / t
         with ctx.Pool(procs) as pool:
-            res = pool.map(_cpu_worker, [(tmp.name, i, sr, brate, vbr_q, abr, budget, kind, vbr_mode) for i in range(procs)],
-                           chunksize=1)
+            res = pool.map(_cpu_worker, [(tmp.name, i, sr, brate, vbr_q, abr, budget, kind, vbr_mode, enc_state)
+                                         for i in range(procs)], chunksize=1)
     finally:
         os.unlink(tmp.name)
     aggregate = sum(a / t for a, t in res)
@@ -342,17 +354,15 @@ def recorded(name):
 def _check_worker(job):
     """One process of the post-check (spawned: no GPU context): the oracle's payload of one saved stream against the
     bytes the GPU left; returns None or a description of the first difference."""
-    pcm_path, idx, stream, frames_path, enc_args = job
+    pcm_path, idx, stream, frames_path, enc_state = job
     import numpy as np
     sys.path.insert(0, os.path.join(ROOT, "deprecated-lame-mirror_amd"))
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import helpers
-    import lamehip
     from lamehip.types import LhFrameOut, struct_diff
     import ctypes as C
     pcm = np.ascontiguousarray(np.load(pcm_path, mmap_mode="r")[idx])
-    enc = lamehip.Encoder(*enc_args[0], require_device=False, **enc_args[1])
-    want = helpers.Oracle().encode_frames(enc.config(), enc.tables(), pcm)
+    want = helpers.Oracle().encode_frames(*encoder_state(enc_state), pcm)
     got = open(frames_path, "rb").read()
     fsz = C.sizeof(LhFrameOut)
     if len(got) != len(want) * fsz:
@@ -365,7 +375,7 @@ def _check_worker(job):
     return None
 
 
-def check_against_oracle(batch, enc_args, host_streams, which, procs=1):
+def check_against_oracle(batch, enc_state, host_streams, which, procs=1):
     """Payload of some of the bench's streams, every frame, against the CPU oracle (test infrastructure, used here only
     as the checker, after the timed region), in `procs' processes at once; raises on the first difference."""
     import multiprocessing as mp
@@ -379,7 +389,7 @@ def check_against_oracle(batch, enc_args, host_streams, which, procs=1):
             fp = os.path.join(tmpd, "frames_%d.bin" % s)
             with open(fp, "wb") as f:
                 f.write(bytes(batch.get_frames(s)))
-            jobs.append((pcm_path, i, s, fp, enc_args))
+            jobs.append((pcm_path, i, s, fp, enc_state))
         if procs > 1 and len(jobs) > 1:
             with mp.get_context("spawn").Pool(min(procs, len(jobs))) as pool:
                 res = pool.map(_check_worker, jobs, chunksize=1)
@@ -483,6 +493,7 @@ def short_run(torch, lamehip, dev, device_index, sr, B, seconds, steps, seed, bu
     (two streams, every frame) and its own roofline block."""
     n = int(seconds * sr)
     enc = lamehip.Encoder(sr, device=device_index, **enc_kw)
+    enc_state = (bytes(enc.config()), bytes(enc.tables()))
     b = lamehip.Batch(enc, B, n, device=device_index)
     pcm = synth_on_device(torch, B, n, sr, seed, dev, bursts_per_s=bursts_per_s)
     for s in range(B):
@@ -500,7 +511,7 @@ def short_run(torch, lamehip, dev, device_index, sr, B, seconds, steps, seed, bu
         parts.append(b.kernel_parts_ms())
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    checked = check_against_oracle(b, ((sr,), dict(enc_kw)), host_streams, which, procs=min(_cpu_budget(), 8))
+    checked = check_against_oracle(b, enc_state, host_streams, which, procs=min(_cpu_budget(), 8))
     assert len(b.pack(0)) > 0
     frames = sum(b.frames(s) for s in range(B))
     b.close()
@@ -510,6 +521,62 @@ def short_run(torch, lamehip, dev, device_index, sr, B, seconds, steps, seed, bu
             "workload": "batch=%d x %.0f s, %d Hz; %s" % (B, seconds, sr, SIGNAL % bursts_per_s), "steps": steps,
             "checked_against_oracle": checked,
             "roofline": roofline_block(frames, sr, sum(kms) / len(kms) / 1e3, mean_parts(parts), pmc_name)}
+
+
+DUMP_MAX_BYTES = 60 * 10 ** 6       # (--dump-outputs: at most 64 MB, the .npy headers included)
+DUMP_STREAMS = 64                   # streams of the batch the output sample is drawn from
+
+
+def dump_outputs(batch, B, path, seed=0x4C414D45):
+    """--dump-outputs DIR: what the caller of the timed path receives from its last step -- the per-frame records the
+    kernels leave in HBM (LhFrameOut: quantised spectra, scale factors, side information; lamehip_batch_get_frames) --
+    one .npy per leaf field, float32 (float64 for the 32-bit fields), for a fixed seeded sample of (stream, frame)
+    pairs that keeps the files under DUMP_MAX_BYTES in all.  The field arrays are indexed like stream_index.npy and
+    frame_index.npy; frames_per_stream.npy holds every stream's frame count."""
+    import numpy as np
+    from lamehip.types import LhFrameOut
+    rec = np.dtype(LhFrameOut)
+
+    def leaves(dt, prefix=""):
+        """(path of field names, file name, bytes one frame's values take in the dump) of every leaf field"""
+        for name in dt.names:
+            if name.rstrip("0123456789") == "pad":          # alignment bytes, not outputs (`padding' is one)
+                continue
+            sub = base = dt.fields[name][0]
+            while base.subdtype:                            # (an array of arrays of granules nests two sub-array types)
+                base = base.subdtype[0]
+            count = sub.itemsize // base.itemsize           # elements of this field per record of `dt'
+            if base.names:
+                for keys, leaf, nbytes in leaves(base, prefix + name + "."):
+                    yield (name,) + keys, leaf, count * nbytes
+            else:
+                yield (name,), prefix + name, count * (8 if base.itemsize == 4 else 4)
+
+    fields = list(leaves(rec))
+    nframes = np.array([batch.frames(s) for s in range(B)], dtype=np.float64)
+    rng = np.random.default_rng(seed)
+    streams = np.sort(rng.choice(B, min(B, DUMP_STREAMS), replace=False))
+    # (per sampled frame: its fields + its two index entries; 64 KB for frames_per_stream.npy's B entries and the headers)
+    budget = DUMP_MAX_BYTES - 8 * B - (64 << 10)
+    per_stream = max(1, budget // (sum(f[2] for f in fields) + 16) // len(streams))
+    cols = {f[1]: [] for f in fields}
+    sidx, fidx = [], []
+    for s in streams:
+        recs = np.frombuffer(bytes(batch.get_frames(int(s))), dtype=rec)
+        pick = np.sort(rng.choice(len(recs), min(len(recs), per_stream), replace=False))
+        sidx.append(np.full(len(pick), s, dtype=np.float64))
+        fidx.append(pick.astype(np.float64))
+        for keys, name, _ in fields:
+            v = recs[pick]
+            for k in keys:
+                v = v[k]
+            cols[name].append(v.astype(np.float64 if v.dtype.itemsize == 4 else np.float32))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "frames_per_stream.npy"), nframes)
+    np.save(os.path.join(path, "stream_index.npy"), np.concatenate(sidx))
+    np.save(os.path.join(path, "frame_index.npy"), np.concatenate(fidx))
+    for name, parts in cols.items():
+        np.save(os.path.join(path, name.replace(".", "_") + ".npy"), np.concatenate(parts))
 
 
 def main():
@@ -527,18 +594,26 @@ def main():
     ap.add_argument("--abr", type=int, default=None, metavar="KBPS", help="ABR at a mean of KBPS instead of CBR")
     ap.add_argument("--bursts", type=float, default=3.0, help="noise bursts per second in the synthetic signal (config[4]: 40)")
     ap.add_argument("--mode", type=int, default=None, help="MPEG mode (1 = joint stereo); default: the library's")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the short runs of BASELINE configs [2] and [4]")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed seeded sample of what the last step computed (the per-frame "
+                         "records of rank 0's streams) to DIR/<field>.npy, float32 / float64, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the oracle check of the timed launch, the CPU baseline, "
+                         "the short runs of other BASELINE configs and the end_to_end object (each can be left out below)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the short runs of BASELINE configs [2] and [4]")
     ap.add_argument("--no-end-to-end", action="store_true",
-                    help="skip the end_to_end object (pinned host PCM -> H2D -> kernel -> D2H -> bytes, pipelined "
-                         "batches of 5 s streams; an extra object, never `value`)")
-    ap.add_argument("--end-to-end", action="store_true", help="(accepted for older command lines; it is the default now)")
+                    help="with --full: skip the end_to_end object (pinned host PCM -> H2D -> kernel -> D2H -> bytes, "
+                         "pipelined batches of 5 s streams; an extra object, never `value`)")
+    ap.add_argument("--end-to-end", action="store_true", help="(accepted for older command lines; part of --full now)")
     ap.add_argument("--check-streams", type=int, default=CHECKED_STREAMS,
-                    help="streams of the timed launch compared with the oracle afterwards (rank 0; default %d)" % CHECKED_STREAMS)
+                    help="with --full: streams of the timed launch compared with the oracle afterwards (rank 0; default %d)"
+                         % CHECKED_STREAMS)
     ap.add_argument("--check-procs", type=int, default=0,
                     help="processes of that comparison (0 = the CPUs this process may use; 1 = in this process: under a "
                          "profiler, which would otherwise attach to every child)")
     args = ap.parse_args()
+    full = args.full
 
     launched = "WORLD_SIZE" in os.environ
     if not launched and args.gpus > 1:
@@ -574,21 +649,24 @@ def main():
     torch.cuda.synchronize()
     for s in range(B):
         batch.set_pcm_device(s, pcm[s, 0].data_ptr(), pcm[s, 1].data_ptr(), n)
-    # host copies for the checks / the CPU leg (rank 0 only): a few whole streams, and the first 20 s of
-    # as many streams as there are physical cores
-    # rank 0: CHECKED_STREAMS streams spread over its block (first and last among them); every other rank: the first and the
-    # last stream of ITS OWN block -- on a node with N devices the output of each is compared with the oracle by its own rank
-    if rank == 0:
-        nck = max(1, min(args.check_streams, B))
-        which = sorted(set(int(round(k * (B - 1) / max(nck - 1, 1))) for k in range(nck)))
-    else:
-        which = sorted(set([0, B - 1]))
-    enc_args = ((sr, args.brate), dict(vbr_q=args.vbr, abr=args.abr, vbr_mode=vbr_mode, **enc_kw))
-    host_streams, host_cpu = [pcm[s].cpu().numpy() for s in which], None
-    if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
-            k = min(_physical_cores(), B)
-            host_cpu = pcm[:k, :, :min(n, int(CPU_SAMPLE_SECONDS * sr))].cpu().numpy()
+    host_streams, host_cpu = None, None
+    if full:
+        # host copies for the checks / the CPU leg (rank 0 only): a few whole streams, and the first 20 s of
+        # as many streams as there are physical cores
+        # rank 0: CHECKED_STREAMS streams spread over its block (first and last among them); every other rank: the first and
+        # the last stream of ITS OWN block -- on a node with N devices the output of each is compared with the oracle by its
+        # own rank
+        if rank == 0:
+            nck = max(1, min(args.check_streams, B))
+            which = sorted(set(int(round(k * (B - 1) / max(nck - 1, 1))) for k in range(nck)))
+        else:
+            which = sorted(set([0, B - 1]))
+        enc_state = (bytes(enc.config()), bytes(enc.tables()))
+        host_streams = [pcm[s].cpu().numpy() for s in which]
+        if rank == 0:
+            if not args.no_cpu_baseline and world == 1:
+                k = min(_physical_cores(), B)
+                host_cpu = pcm[:k, :, :min(n, int(CPU_SAMPLE_SECONDS * sr))].cpu().numpy()
     del pcm
     torch.cuda.synchronize()
     frames = sum(batch.frames(s) for s in range(B))
@@ -613,14 +691,21 @@ def main():
     own_cpu = time.process_time() - c0
     barrier()
     dt = rdv.max(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(batch, B, args.dump_outputs)
     # what each rank did, for the one line rank 0 prints (timing scalars only; no stream data ever crosses ranks)
-    # every rank checks its own streams (after the timed region; a difference ends the rank with an error, and with it the run)
-    checked = check_against_oracle(batch, enc_args, host_streams, which,
-                                   procs=(args.check_procs or _cpu_budget()) if rank == 0 else 1)
-    per_rank = rdv.gather([rank, device_index, lo, hi, own_dt, own_cpu, sum(kernel_ms) / len(kernel_ms), float(checked["streams"])])
+    # --full: every rank checks its own streams (after the timed region; a difference ends the rank with an error, and with it
+    # the run)
+    checked = None
+    if full:
+        checked = check_against_oracle(batch, enc_state, host_streams, which,
+                                       procs=(args.check_procs or _cpu_budget()) if rank == 0 else 1)
+    per_rank = rdv.gather([rank, device_index, lo, hi, own_dt, own_cpu, sum(kernel_ms) / len(kernel_ms),
+                           float(checked["streams"]) if checked else 0.0])
 
     if rank == 0:
-        assert len(batch.pack(0)) > 0           # and the payload survives the host packer's consistency checks
+        if full:
+            assert len(batch.pack(0)) > 0       # and the payload survives the host packer's consistency checks
         audio_s = world * B * args.seconds * args.steps
         value = audio_s / dt
         kavg = sum(kernel_ms) / len(kernel_ms) / 1e3
@@ -654,19 +739,21 @@ def main():
                           # host CPU seconds this rank's process burned per wall second of its timed region: the
                           # kernel path needs no host work, the rest is the runtime waiting for the stream
                           "host_cpu_per_wall_s": round(r[5] / r[4], 3),
-                          # streams of this rank's own block that its own process compared with the oracle after the timed
-                          # region (a difference would have ended the run)
-                          "checked_streams": int(r[7]), "checked": "identical"} for r in per_rank],
+                          # --full: streams of this rank's own block that its own process compared with the oracle after
+                          # the timed region (a difference would have ended the run)
+                          **({"checked_streams": int(r[7]), "checked": "identical"} if full else {})} for r in per_rank],
             "collectives_on_data_path": 0,
             "pipeline": ({"kind": "split", "kernels_ms_avg": dict(zip(("analysis", "subband", "encode"),
                           [round(sum(p[1][k] for p in parts_ms) / len(parts_ms), 3) for k in range(3)]))}
                          if parts_ms and parts_ms[0][0] else {"kind": "fused"}),
             "roofline": roofline_block(frames, sr, kavg, mean_parts(parts_ms), pmc_record_for(args)),
-            "checked_against_oracle": checked,
         }
+        if full:
+            res["checked_against_oracle"] = checked
         if host_cpu is not None:
-            res["cpu_baseline"] = cpu_baseline(host_cpu, sr, args.brate, vbr_q=args.vbr, abr=args.abr, vbr_mode=vbr_mode)
-        if not args.no_extras and world == 1 and args.vbr is None and args.abr is None:
+            res["cpu_baseline"] = cpu_baseline(host_cpu, sr, args.brate, enc_state, vbr_q=args.vbr, abr=args.abr,
+                                               vbr_mode=vbr_mode)
+        if full and not args.no_extras and world == 1 and args.vbr is None and args.abr is None:
             batch.close()
             batch = None
             res["extra"] = {
@@ -680,7 +767,7 @@ def main():
                 "mpeg2_22k_cbr64": short_run(torch, lamehip, dev, device_index, 22050, 1024, 10.0, 2, 7000, 3.0,
                                              "r06_pmc_lsf.json", brate=64),
             }
-        if not args.no_end_to_end and not args.no_extras and world == 1:
+        if full and not args.no_end_to_end and not args.no_extras and world == 1:
             if batch is not None:
                 batch.close()
                 batch = None

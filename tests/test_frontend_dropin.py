@@ -74,7 +74,7 @@ def input_files(directory):
 
 
 @pytest.mark.skipif(not os.path.exists("/root/reference/frontend/lame_main.c"), reason="needs the reference's frontend sources")
-def test_reference_frontend_links_against_liblamehip():
+def test_reference_frontend_links_against_liblamehip(tmp_path):
     """`make frontend' links with -Wl,--no-undefined: every lame_* / get_lame_* symbol the frontend objects ask for is
     exported by liblamehip.so (the id3tag_* ones by the shim); and without a device it refuses to encode."""
     helpers.locked_make(["frontend"], os.path.join(ROOT, "oracle"))
@@ -106,7 +106,7 @@ def test_reference_frontend_links_against_liblamehip():
     import torch
     if not torch.cuda.is_available():
         with open(os.devnull, "w") as null:
-            r = subprocess.run([EXE, "--quiet", "-b", "128", os.path.join(ROOT, "tests", "golden", "testcase.wav"), "/tmp/_dropin.mp3"],
+            r = subprocess.run([EXE, "--quiet", "-b", "128", os.path.join(ROOT, "tests", "golden", "testcase.wav"), str(tmp_path / "o.mp3")],
                                stdout=null, stderr=subprocess.PIPE, text=True)
         assert r.returncode != 0 and "no HIP device" in r.stderr
 

@@ -196,7 +196,7 @@ def _full_batch_against_oracle(sr, n, burst_interval, seed0, **enc_kw):
 def test_full_batch_every_stream_matches_oracle():
     """BASELINE config[1]'s batch (1024 streams, CBR 128, 44.1 kHz stereo) with 1024 DIFFERENT signals of the bench's recipe,
     1.5 s each.  The launch is the headline's -- 1024 workgroups, two waves per SIMD, every SIMD shared by two streams -- only
-    shorter; bench.py's own post-check compares 64 streams of the 60 s launch."""
+    shorter; `bench.py --full` checks 64 streams of the 60 s launch the same way."""
     _full_batch_against_oracle(44100, 44100 * 3 // 2, 1.0 / 3, 91000, brate=128)
 
 
@@ -666,7 +666,7 @@ def test_bench_spawns_its_own_ranks():
     import subprocess
     import sys
     out = subprocess.run([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "2", "--streams", "16",
-                          "--seconds", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras"],
+                          "--seconds", "2", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras"],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900,
                          env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert out.returncode == 0, out.stderr[-2000:]
@@ -689,7 +689,7 @@ def test_bench_eight_ranks_shard_a_batch_without_any_collective():
     import subprocess
     import sys
     out = subprocess.run([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "8", "--streams", "32",
-                          "--seconds", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras"],
+                          "--seconds", "2", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras"],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500,
                          env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert out.returncode == 0, out.stderr[-2000:]
@@ -724,7 +724,7 @@ def test_bench_under_the_torch_launcher():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29677", os.path.join(helpers.ROOT, "bench.py"),
            "--gpus", "2", "--streams", "16", "--seconds", "2", "--steps", "1", "--warmup", "1",
-           "--no-cpu-baseline", "--no-extras"]
+           "--full", "--no-cpu-baseline", "--no-extras"]
     out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900,
                          env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert out.returncode == 0, out.stderr[-2000:]

@@ -33,9 +33,9 @@ fi
 # the search's segments (make -C deprecated-lame-mirror_amd/csrc trace) and the analysis kernels' phases (make aprof)
 [ -f deprecated-lame-mirror_amd/lamehip/liblamehip_trace.so ] && LAMEHIP_LIB=$PWD/deprecated-lame-mirror_amd/lamehip/liblamehip_trace.so python tools/trace_profile.py 1024 4 > profiles/r06_trace_profile.txt 2>&1
 [ -f deprecated-lame-mirror_amd/lamehip/liblamehip_aprof.so ] && LAMEHIP_LIB=$PWD/deprecated-lame-mirror_amd/lamehip/liblamehip_aprof.so python tools/an_profile.py 1024 4 > profiles/r06_an_profile.txt 2>&1
-python bench.py 2>/dev/null | grep '^{"metric"' > profiles/r06_bench_default.json
-python bench.py --vbr 2 --no-extras 2>/dev/null | grep '^{"metric"' > profiles/r06_bench_vbr2.json
-python bench.py --vbr 2 --vbr-old --no-extras 2>/dev/null | grep '^{"metric"' > profiles/r06_bench_vbrold2.json
+python bench.py --full 2>/dev/null | grep '^{"metric"' > profiles/r06_bench_default.json
+python bench.py --full --vbr 2 --no-extras 2>/dev/null | grep '^{"metric"' > profiles/r06_bench_vbr2.json
+python bench.py --full --vbr 2 --vbr-old --no-extras 2>/dev/null | grep '^{"metric"' > profiles/r06_bench_vbrold2.json
 mkdir -p gpurun_out/profiles_r06 && cp profiles/r06* gpurun_out/profiles_r06/
 cut -c1-600 profiles/r06_bench_default.json
 cat profiles/r06_pmc.json
