@@ -302,8 +302,20 @@ struct LhNoiseRes {             /* calc_noise_result */
 #define LQ_ORG_T2   132         /* tables 2 / 3: rows 8..10, columns 4..6 */
 #define LQ_ORG_T1   136         /* table 1: rows 8..9, columns 8..9 */
 
+/* The usual-case stages keep calc_noise's squared errors in xrpow[] band by band, each long band 0 .. 20 padded to a multiple
+ * of eight terms (LhQS.pad, lh_dev_qloop.h): with the 44.1 kHz table, the widest that lh_cfg_class admits (sfb_l[21] <= 418),
+ * the padded bands end at LQ_SQ_END on the nose.  The hand-written band sum (lq_band_sums_pad) reads whole blocks of sixteen
+ * terms, one block ahead of the additions: a lane with n terms reads 16 (ceil(n / 16) + 1) of them, at most LQ_SQ_AHEAD past its
+ * band's padded end (n = 1 .. 8 modulo 16) -- what it reads there is never added.  The squares of lines that belong to no sum go
+ * to the two words at LQ_SQ_DUMP, which must lie behind everything that is added.  Nothing checks the band table on the
+ * device; tests/test_route_census.py checks, for the tables of every output rate, that lh_cfg_class's `sfb_l[21] <= 418' is
+ * the same condition as `the padded bands end at or before LQ_SQ_END', and restates the walk of the loop. */
+#define LQ_SQ_END 488
+#define LQ_SQ_AHEAD 24
+#define LQ_SQ_DUMP 568
+
 struct LhChanLds {
-    float   xrpow[576];         /* the CBR search keeps xrpow in registers and uses this as calc_noise's scratch */
+    float   xrpow[576];         /* the CBR search keeps xrpow in registers and uses this as calc_noise's scratch (see above) */
     union {
         float   save_xrpow[576];        /* scratch of the VBR loop and of best_huffman_divide */
         uint32_t hl3_big[2][256];       /* while the CBR search runs: [0] = ESC grid, [1] = tables 13..15 */
@@ -330,6 +342,9 @@ struct LhChanLds {
     float   zero2[2];           /* two zeros on an 8-byte boundary: where masked-out term loads are redirected */
     float   pad2[2];            /* keeps sizeof a multiple of 16 */
 };
+static_assert(LQ_SQ_END + LQ_SQ_AHEAD <= LQ_SQ_DUMP && LQ_SQ_DUMP + 2 <= 576, "the padded band sums read and add inside xrpow[], in front of the dump words");
+static_assert(sizeof(LhChanLds) - (__builtin_offsetof(LhChanLds, xrpow) + sizeof(float[576])) >= sizeof(float[LQ_SQ_AHEAD]),
+              "LDS of the same channel follows xrpow[] for at least the band sums' read-ahead");
 
 /* hot lookup tables of the quantiser, staged into LDS for the iteration-loop phase
  * (they live behind xr in the region the PCM window occupied earlier in the frame) */
@@ -585,6 +600,16 @@ lh_ctx_hot(LhCtx & c)
     c.rate8k = 0;
 #endif
 }
+
+/* route census of the test build (enum LhRoute, lh_device.h): lane 0 of the wave that takes route k counts it in the stream's
+ * state in HBM -- a plain read-modify-write, the wave is the counter's only writer.  Nothing in any other build. */
+#ifdef LH_DEBUG_DUMP
+#define LH_ROUTE(c, k) do { if ((c).lane == 0) (c).st->dbg_route[(c).wave][k] += 1u; } while (0)
+#else
+#define LH_ROUTE(c, k) do { } while (0)
+#endif
+/* (the ZERO_* route of a block type) */
+#define LH_ROUTE_ZERO(bt) ((bt) == LH_NORM_TYPE ? LH_RT_ZERO_norm : (bt) == LH_SHORT_TYPE ? LH_RT_ZERO_short : LH_RT_ZERO_other)
 
 /* The context reaches an out-of-line stage through per-lane memory, which hides from the
  * compiler that its pointers address HBM; routing them through the global address space once

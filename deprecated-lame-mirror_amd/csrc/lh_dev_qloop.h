@@ -71,7 +71,8 @@ struct LhQS {
     mutable LhTr tr;            /* development aid: cycles per segment of the search (lh_dev_common.h) */
 #endif
 };
-#define LQ_SQ_DUMP 568          /* (floats; the padded bands end at 488 for the widest table: checked in lq_load) */
+/* (LQ_SQ_END / LQ_SQ_AHEAD / LQ_SQ_DUMP: where the padded bands end, how far the sums read ahead, where the squares of no band go --
+ * beside LhChanLds.xrpow in lh_dev_common.h, with the asserts; the band table itself is checked by tests/test_route_census.py) */
 
 LH_DEVFN int
 lq_bit(uint64_t m, int b)

@@ -796,6 +796,8 @@ lh_vbr_granule_body(int qch, int gr, int rch, int pass, int gate, int target, in
     }
     LH_PA(16, t_a);
     nonzero = lh_init_xrpow(c, Q, R, g, xr);    /* silent granules: all of ix[0] cleared */
+    if (pass == 0 && !nonzero)
+        LH_ROUTE(c, LH_ROUTE_ZERO(R.block_type));
     if (pass == 0 && s == 0) {
         sv.mnc = R.mnc;
         sv.ath_over = R.ath_over;
@@ -1078,10 +1080,14 @@ lh_vbr_frame(LhFrameOut * fo_in, int mode_ext, int msoff)
     LH_SYNC_WG();
     for (int gr = 0; gr < ngr; gr++) {
         if (w < nch)
-            if (!LH_IS_LSF && lh_uni_i(L.block_type[gr][w]) == LH_NORM_TYPE)
+            if (!LH_IS_LSF && lh_uni_i(L.block_type[gr][w]) == LH_NORM_TYPE) {
+                LH_ROUTE(c, LH_RT_V_n);
                 lh_vbr_granule_n(w, gr, msoff + w, max_bits[gr][w], substep, &fo->gr[gr][w], fo->gr[0][w].scalefac);
-            else
+            }
+            else {
+                LH_ROUTE(c, LH_RT_V_gen);
                 lh_vbr_granule(w, gr, msoff + w, 0, max_bits[gr][w], 0, substep, &fo->gr[gr][w], fo->gr[0][w].scalefac);
+            }
         else {
             /* mono: no second channel, its payload slot is all zero */
             uint32_t *z = (uint32_t *) &fo->gr[gr][w];
@@ -1123,9 +1129,11 @@ lh_vbr_frame(LhFrameOut * fo_in, int mode_ext, int msoff)
         lh_vbr_budgets(ngr, nch, max_bits, use_ch, use_gr, max_fr, max_ch);
         LH_SYNC_WG();
         for (int gr = 0; gr < ngr; gr++)
-            if (w < nch)
+            if (w < nch) {
+                LH_ROUTE(c, LH_RT_V_PASS2);
                 lh_vbr_granule(w, gr, msoff + w, 1, max_bits[gr][w], max_ch[gr][w], substep, &fo->gr[gr][w],
                                fo->gr[0][w].scalefac);
+            }
         LH_SYNC_WG();
         used = 0;
         for (int gr = 0; gr < ngr; gr++)

@@ -134,20 +134,38 @@ lh_vbrold_granule(int qch, int gr, int rch, int pass, int min_bits, int max_bits
         lh_rg_put(c, R, g);
         int const cls = lh_uni_i(lh_vbrold_class(c, R.block_type, R.substep_shaping));
         if (lq_needs_tail(c, Q, R)) {
-            if (cls == 2)
+            if (cls == 2) {
+                if (pass == 0)
+                    LH_ROUTE(c, LH_RT_O5n);
                 lq_vbrold_stage5n(qch, gr, min_bits, max_bits, pass != 0);
-            else if (cls == 1)
+            }
+            else if (cls == 1) {
+                if (pass == 0)
+                    LH_ROUTE(c, LH_RT_O5m);
                 lq_vbrold_stage5m(qch, gr, min_bits, max_bits, pass != 0);
-            else
+            }
+            else {
+                if (pass == 0)
+                    LH_ROUTE(c, LH_RT_O5);
                 lq_vbrold_stage5(qch, gr, min_bits, max_bits, pass != 0);
+            }
         }
         else {
-            if (cls == 2)
+            if (cls == 2) {
+                if (pass == 0)
+                    LH_ROUTE(c, LH_RT_O4n);
                 lq_vbrold_stage4n(qch, gr, min_bits, max_bits, pass != 0);
-            else if (cls == 1)
+            }
+            else if (cls == 1) {
+                if (pass == 0)
+                    LH_ROUTE(c, LH_RT_O4m);
                 lq_vbrold_stage4m(qch, gr, min_bits, max_bits, pass != 0);
-            else
+            }
+            else {
+                if (pass == 0)
+                    LH_ROUTE(c, LH_RT_O4);
                 lq_vbrold_stage4(qch, gr, min_bits, max_bits, pass != 0);
+            }
         }
         R = lh_uniform(L.rg[qch].R);
         g = lh_uniform(L.rg[qch].g);
@@ -158,6 +176,8 @@ lh_vbrold_granule(int qch, int gr, int rch, int pass, int min_bits, int max_bits
             Q.ix[0][i] = 0;
         LH_WAVE_SYNC();
     }
+    if (!live && pass == 0)
+        LH_ROUTE(c, LH_ROUTE_ZERO(R.block_type));
     /* park what a further pass starts from */
     LH_WAVE_SYNC();
     if (s <= LH_SFBMAX)
@@ -288,7 +308,8 @@ lh_vbrold_frame(LhFrameOut * fo_in, int mode_ext, int msoff)
         {
             int     fits = used_bits <= lh_vbr_full_bits(cfg, bitrate_index, ResvSize, &dummy, &dummy);
 #ifdef LH_EMU
-            /* test hook of the CPU emulator build only (see oracle/orc_vbr_old.c): real input does not get here */
+            /* test hook of the CPU emulator build only (see oracle/orc_vbr_old.c): no input is known that gets here on its own
+             * (tests/test_route_census.py::test_old_vbr_bitpressure_grid looks for one and counts the passes: LH_RT_OLD_PASS_*) */
             if (getenv("LH_TEST_FORCE_PRESSURE") && pass < atoi(getenv("LH_TEST_FORCE_PRESSURE")))
                 fits = 0;
 #endif
@@ -302,6 +323,7 @@ lh_vbrold_frame(LhFrameOut * fo_in, int mode_ext, int msoff)
             break;
         }
         /* bitpressure_strategy (reference quantize.c:1456-1480): more noise allowed towards the top, smaller budgets */
+        LH_ROUTE(c, pass == 0 ? LH_RT_OLD_PASS_FRAMES : LH_RT_OLD_PASS_EXTRA);
         LH_SYNC_WG();
         for (int gr = 0; gr < LH_NGR; gr++) {
             if (w < nch) {

@@ -17,6 +17,25 @@ extern "C" {
 #define LH_EMIT_HQ_MAX 256      /* frame headers that can be pending inside a stretch of main data (device bit packer; the host packer and the reference hold 256 as well: MAX_HEADER_BUF) */
 #define LH_XMIN_N 61            /* 22 long + 13*3 short values of III_psy_xmin */
 
+/* Which of the out-of-line variants of a stage a granule took (TEST BUILD ONLY: counted by the LH_DEBUG_DUMP build,
+ * LhStreamState.dbg_route, through LH_ROUTE() of lh_dev_common.h; the product build counts nothing).  One enumerator per
+ * route; tests/golden/route_names.json holds the same names in the same order (tests/test_route_census.py compares). */
+enum LhRoute {
+    /* the CBR / ABR search (lh_encode_frame): tail slots 4 / 5 x {general, n, m, s, t} */
+    LH_RT_S4, LH_RT_S5, LH_RT_S4n, LH_RT_S5n, LH_RT_S4m, LH_RT_S5m, LH_RT_S4s, LH_RT_S5s, LH_RT_S4t, LH_RT_S5t,
+    /* the old VBR loop's search (lh_vbrold_granule; a frame's first pass only) */
+    LH_RT_O4, LH_RT_O5, LH_RT_O4n, LH_RT_O5n, LH_RT_O4m, LH_RT_O5m,
+    /* frames of the old VBR loop that went round bitpressure_strategy at least once / passes beyond the first, summed */
+    LH_RT_OLD_PASS_FRAMES, LH_RT_OLD_PASS_EXTRA,
+    /* granule preparation and finish of the CBR / ABR loop */
+    LH_RT_PREP_n, LH_RT_PREP_gen, LH_RT_FIN_n, LH_RT_FIN_gen,
+    /* the new VBR loop: first pass per variant, granules searched a second time */
+    LH_RT_V_n, LH_RT_V_gen, LH_RT_V_PASS2,
+    /* granules without a search (nothing to quantise), by block type: normal, short, start / stop */
+    LH_RT_ZERO_norm, LH_RT_ZERO_short, LH_RT_ZERO_other,
+    LH_NROUTE
+};
+
 typedef struct LhStreamState {
     /* psycho-acoustic model (PsyStateVar_t) */
     float   nb_l1[4][LH_CBANDS];
@@ -62,7 +81,9 @@ typedef struct LhStreamState {
     /* TEST BUILD ONLY (make dump -> liblamehip_dump.so, tests/test_stage_fixtures.py): what the stages of the last
      * frame handed on, [gr][ch] -- the spectra as the quantiser left them in place (after the mid/side rotation and the
      * short-block reordering), the allowed noise calc_xmin formed and the band energies / thresholds it formed it from,
-     * the smoothed perceptual entropies and the bit budgets of the CBR loop */
+     * the smoothed perceptual entropies and the bit budgets of the CBR loop.  In front of them the route census:
+     * [wave = channel][enum LhRoute], cumulative since lh_state_init; each counter has one writer (lane 0 of its wave) */
+    uint32_t dbg_route[2][LH_NROUTE];
     float   dbg_xr[2][2][576];
     float   dbg_xmin[2][2][LH_SFBMAX + 1];
     float   dbg_en[2][2][LH_XMIN_N + 3];

@@ -239,6 +239,7 @@ lh_prepare_granule(const LhCtx & c, int ch, int gr, int msoff, int substep)
     LhGrR   g;
     int     nonzero;
     int const usual = lh_uni_i(lh_granule_is_usual(c, L.block_type[gr][ch], substep));
+    LH_ROUTE(c, usual ? LH_RT_PREP_n : LH_RT_PREP_gen);
     if (usual)
         lh_init_outer_loop_n(ch, gr, substep);
     else
@@ -676,41 +677,65 @@ lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry)
                 int const usual = lh_uni_i(lh_granule_is_usual(c, R.block_type, R.substep_shaping));
                 int const ushort = lh_uni_i(lh_granule_is_usual_short(c, R.block_type, R.substep_shaping));
                 if (lq_needs_tail(c, Q, R)) {
-                    if (usual == 2)
+                    if (usual == 2) {
+                        LH_ROUTE(c, LH_RT_S5n);
                         lq_outer_loop_stage5n(ch, gr, targ_bits[ch]);
-                    else if (usual == 1)
+                    }
+                    else if (usual == 1) {
+                        LH_ROUTE(c, LH_RT_S5m);
                         lq_outer_loop_stage5m(ch, gr, targ_bits[ch]);
-                    else if (ushort == 2)
+                    }
+                    else if (ushort == 2) {
+                        LH_ROUTE(c, LH_RT_S5s);
                         lq_outer_loop_stage5s(ch, gr, targ_bits[ch]);
-                    else if (ushort == 1)
+                    }
+                    else if (ushort == 1) {
+                        LH_ROUTE(c, LH_RT_S5t);
                         lq_outer_loop_stage5t(ch, gr, targ_bits[ch]);
-                    else
+                    }
+                    else {
+                        LH_ROUTE(c, LH_RT_S5);
                         lq_outer_loop_stage5(ch, gr, targ_bits[ch]);
+                    }
                 }
                 else {
-                    if (usual == 2)
+                    if (usual == 2) {
+                        LH_ROUTE(c, LH_RT_S4n);
                         lq_outer_loop_stage4n(ch, gr, targ_bits[ch]);
-                    else if (usual == 1)
+                    }
+                    else if (usual == 1) {
+                        LH_ROUTE(c, LH_RT_S4m);
                         lq_outer_loop_stage4m(ch, gr, targ_bits[ch]);
-                    else if (ushort == 2)
+                    }
+                    else if (ushort == 2) {
+                        LH_ROUTE(c, LH_RT_S4s);
                         lq_outer_loop_stage4s(ch, gr, targ_bits[ch]);
-                    else if (ushort == 1)
+                    }
+                    else if (ushort == 1) {
+                        LH_ROUTE(c, LH_RT_S4t);
                         lq_outer_loop_stage4t(ch, gr, targ_bits[ch]);
-                    else
+                    }
+                    else {
+                        LH_ROUTE(c, LH_RT_S4);
                         lq_outer_loop_stage4(ch, gr, targ_bits[ch]);
+                    }
                 }
                 R = lh_uniform(L.rg[ch].R);
                 g = lh_uniform(L.rg[ch].g);
                 LH_PA(5, t_ol);
             }
+            else
+                LH_ROUTE(c, LH_ROUTE_ZERO(R.block_type));
             LH_PT(t_fin);
             lh_rg_put(c, R, g);
             if (lh_uni_i(lh_granule_is_usual(c, R.block_type, R.substep_shaping))) {
+                LH_ROUTE(c, LH_RT_FIN_n);
                 lh_best_scalefac_store_n(ch, gr, fo->gr[0][ch].scalefac, L.block_type[0][ch]);
                 if (cfg->use_best_huffman == 1)
                     lh_best_huffman_divide_n(ch);
             }
             else {
+                LH_ROUTE(c, LH_RT_FIN_gen);
                 lh_best_scalefac_store(ch, gr, fo->gr[0][ch].scalefac, L.block_type[0][ch]);
                 if (cfg->use_best_huffman == 1)
                     lh_best_huffman_divide(ch);

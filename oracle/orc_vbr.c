@@ -510,6 +510,10 @@ vbr_quantize_count(const OrcVbrGr * V)
     return V->gi->part2_3_length;
 }
 
+/* census for the tests (tests/test_route_census.py): frames whose granules were searched a second time -- cumulative,
+ * the caller clears it */
+int     orc_vbr_pass2_frames = 0;
+
 /* bits (incl. scalefactors) with these step indices (tryThatOne, reference vbrquantize.c:1139-1150) */
 static int
 vbr_try(const OrcVbrGr * V, const int steps[LH_SFBMAX], int vbrmax)
@@ -718,6 +722,7 @@ vbr_encode_frame(OrcStream * S, float xr34[2][2][576], float xmin[2][2][LH_SFBMA
             return use_fr;
     }
     /* too many bits: fix a budget per granule and channel */
+    orc_vbr_pass2_frames++;
     ok = 1;
     sum_fr = 0;
     for (gr = 0; gr < S->cfg->mode_gr; ++gr) {

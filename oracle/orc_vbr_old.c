@@ -137,6 +137,10 @@ vbr_old_bitpressure(OrcStream * S, float l3_xmin[2][2][LH_SFBMAX], int min_bits[
         }
 }
 
+/* Census for the tests (tests/test_route_census.py): frames that went round bitpressure_strategy at least once and the
+ * passes beyond the first, summed -- cumulative, the caller clears them. */
+int     orc_old_pass_frames = 0, orc_old_pass_extra = 0;
+
 /* reference quantize.c:1491-1578 */
 void
 orc_vbr_old_iteration_loop(OrcStream * S, float pe[2][2], const float ms_ener_ratio[2], const OrcRatio ratio[2][2])
@@ -147,7 +151,7 @@ orc_vbr_old_iteration_loop(OrcStream * S, float pe[2][2], const float ms_ener_ra
     int     frameBits[16];
     int     used_bits, bits, mean_bits;
     int     min_bits[2][2], max_bits[2][2];
-    int     ch, gr, analog_silence;
+    int     ch, gr, analog_silence, pass = 0;
 
     /* Test hook: the budgets of VBR_old_prepare add up to what the largest frame holds and every search stays inside
      * its budget, so real input does not reach the second pass (only a search that ends at global_gain 255 could);
@@ -178,6 +182,10 @@ orc_vbr_old_iteration_loop(OrcStream * S, float pe[2][2], const float ms_ener_ra
         bits = ResvFrameBegin(S, &mean_bits);
         if (used_bits <= bits && forced-- <= 0)
             break;
+        if (pass++ == 0)
+            orc_old_pass_frames++;
+        else
+            orc_old_pass_extra++;
         vbr_old_bitpressure(S, l3_xmin, min_bits, max_bits);
     }
     for (gr = 0; gr < cfg->mode_gr; gr++)

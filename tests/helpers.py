@@ -83,6 +83,23 @@ class Oracle:
                                    right.ctypes.data_as(C.c_void_p), C.c_long(n), out, nf, None)
         return out
 
+    def encode_frames_census(self, cfg, tab, pcm):
+        """encode_frames plus what tests/test_route_census.py predicts routes from: the spectra as the quantiser left them
+        in place, float32 [frame][gr][ch][576] (after the mid/side rotation, the short-block reordering and, under the old
+        VBR loop, the analog-silence edit of the top band), and the loops' pass counters for this stream."""
+        left = np.ascontiguousarray(pcm[0], dtype=np.int16)
+        right = np.ascontiguousarray(pcm[1], dtype=np.int16)
+        n = len(left)
+        nf = self.lib.orc_total_frames_fs(C.c_long(n), 576 * cfg.mode_gr)
+        out = (LhFrameOut * nf)()
+        xr = np.zeros((nf, 2, 2, 576), np.float32)
+        names = ("orc_old_pass_frames", "orc_old_pass_extra", "orc_vbr_pass2_frames")
+        for k in names:
+            C.c_int.in_dll(self.lib, k).value = 0
+        self.lib.orc_encode_stream(C.byref(cfg), C.byref(tab), left.ctypes.data_as(C.c_void_p),
+                                   right.ctypes.data_as(C.c_void_p), C.c_long(n), out, nf, xr.ctypes.data_as(C.c_void_p))
+        return out, xr, {k: C.c_int.in_dll(self.lib, k).value for k in names}
+
 
 class Reference:
     """The real reference encoder built by oracle/Makefile (only in trees where

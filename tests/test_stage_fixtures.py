@@ -19,6 +19,10 @@ import helpers
 DUMP_LIB = os.path.join(helpers.ROOT, "deprecated-lame-mirror_amd", "lamehip", "liblamehip_dump.so")
 NAMES = ("cbr128_js_44k", "vbr2_js_44k")
 TAIL_FLOATS = 2 * 2 * 576 + 2 * 2 * 40 + 2 * (2 * 2 * 64) + 4 + 4 + 1 + 3
+# in front of those words the dump build keeps the route census (LhStreamState.dbg_route, tests/test_route_census.py):
+# two waves x one counter per name of tests/golden/route_names.json; everything here is read from the end of the state
+with open(os.path.join(helpers.ROOT, "tests", "golden", "route_names.json")) as _f:
+    ROUTE_WORDS = 2 * len(json.load(_f))
 
 # runs in a child process: the binding loads ONE library per process (LAMEHIP_LIB)
 CHILD = r'''
@@ -73,7 +77,7 @@ def test_stage_fixtures_are_committed_and_the_dump_build_exists():
     assert os.path.exists(DUMP_LIB), "make -C deprecated-lame-mirror_amd/csrc dump"
     dump = C.CDLL(DUMP_LIB)
     prod = C.CDLL(os.path.join(helpers.ROOT, "deprecated-lame-mirror_amd", "lamehip", "liblamehip.so"))
-    assert dump.lamehip_abi_sizeof(4) == prod.lamehip_abi_sizeof(4) + 4 * TAIL_FLOATS
+    assert dump.lamehip_abi_sizeof(4) == prod.lamehip_abi_sizeof(4) + 4 * (ROUTE_WORDS + TAIL_FLOATS)
 
 
 @pytest.mark.gpu

@@ -51,8 +51,10 @@ CASES = [
     (dict(brate=0), {}),
     (dict(brate=128), {"VBR_quality": 4.7}), (dict(abr=140), {"VBR_quality": 6.3}),   # the fraction reaches the CBR / ABR tables too
     (dict(brate=176), {}), (dict(brate=144), {}),      # lowpass from the bitrate as asked, frame size from the rounded one
-    # the old VBR loop (lame_set_VBR(vbr_rh), the frontend's --vbr-old); a low -B makes it raise the allowed noise
-    # and search again (bitpressure_strategy)
+    # the old VBR loop (lame_set_VBR(vbr_rh), the frontend's --vbr-old).  A low -B shrinks the budgets the searches get; it does NOT
+    # send the loop round bitpressure_strategy (raise the allowed noise, search again): the budgets are scaled to the largest
+    # frame before the search, so what the searches use always fits -- tests/test_route_census.py::test_old_vbr_bitpressure_grid
+    # searches a grid of such settings for a counter-example and counts the passes on the device (OLD_PASS_FRAMES)
     (dict(vbr_q=2, vbr_mode=2), {}), (dict(vbr_q=4, vbr_mode=2), {"VBR_max_bitrate_kbps": 96}),
     (dict(vbr_q=0, vbr_mode=2), {"VBR_max_bitrate_kbps": 64}), (dict(vbr_q=5, vbr_mode=2), {"VBR_min_bitrate_kbps": 128, "VBR_hard_min": 1}),
     (dict(vbr_q=3, vbr_mode=2), {"force_ms": 1}), (dict(vbr_q=6, vbr_mode=2), {"disable_reservoir": 1}),
