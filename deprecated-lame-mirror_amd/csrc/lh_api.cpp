@@ -1534,6 +1534,10 @@ batch_split_denied(void)
     return e && e[0] == '1';
 }
 
+extern "C" int lh_launch_resample(const LhRsParams * p, const float *bank, const LhRsBlock * trunk, const LhRsBlock * tails,
+                                  const LhRsStream * streams, int nstreams, int max_blocks, const int16_t * pcm, float *pcmf,
+                                  void *stream);
+
 struct lamehip_batch {
     int     device;
     LhConfig cfg;
@@ -1567,6 +1571,25 @@ struct lamehip_batch {
     float  *d_pcmf;             /* [B][2][capf] */
     long    capf;
     std::vector < int >padding; /* encoder_padding per stream (tag frame) */
+    /* ... or, after lamehip_batch_set_device_resampling, on the device: the s16 pool d_pcm holds the input ([B][2][cap] at
+     * the input rate, with its pinned mirror and device-side entry points as in a batch that does not convert), the host
+     * only plans (lh_rs_trunk_extend / lh_rs_plan_tail: the blocks all streams share, and each stream's own last blocks) and
+     * lamehip_batch_encode launches lh_resample_dev.hip over the streams declared since their last conversion */
+    int     dev_rs;
+    int     pcm_given;          /* PCM (or a length, or the mirror) has been handed over: the converter's place is settled */
+    LhRsTrunk trunk;
+    std::vector < long >len_in; /* input samples per stream (len[] is the converted length) */
+    std::vector < std::vector < LhRsBlock > >tail;
+    std::vector < char >rs_dirty;       /* declared since the stream's last conversion */
+    std::vector < LhRsBlock > h_tails;  /* what the last launch's plan consisted of besides the trunk */
+    std::vector < LhRsStream > h_rs_streams;
+    float  *d_rs_bank;
+    LhRsBlock *d_rs_trunk, *d_rs_tails;
+    LhRsStream *d_rs_streams;
+    long    rs_trunk_cap, rs_trunk_up, rs_tails_cap;    /* blocks: room in d_rs_trunk, uploaded so far, room in d_rs_tails */
+    hipEvent_t ev_rs[2];
+    int     rs_ran;             /* the last lamehip_batch_encode converted something (between ev_rs[0] and ev_rs[1]) */
+    float   rs_ms;
     /* incremental use (lamehip_batch_append ...): samples in the pool / frames encoded per stream, a
      * packer and the bytes not yet drained per stream, and the pinned staging area of the next
      * lamehip_batch_encode_available (see h_stage below) */
@@ -1924,6 +1947,15 @@ lamehip_batch_create_on(int device, const lame_t proto, int nstreams, long capac
     b->d_pcmf = nullptr;
     b->capf = 0;
     b->padding.assign((size_t) nstreams, 0);
+    b->dev_rs = b->pcm_given = 0;
+    memset(&b->trunk, 0, sizeof(b->trunk));
+    b->d_rs_bank = nullptr;
+    b->d_rs_trunk = b->d_rs_tails = nullptr;
+    b->d_rs_streams = nullptr;
+    b->rs_trunk_cap = b->rs_trunk_up = b->rs_tails_cap = 0;
+    b->ev_rs[0] = b->ev_rs[1] = nullptr;
+    b->rs_ran = 0;
+    b->rs_ms = 0;
     b->incremental = 0;
     b->h_stage = b->d_stage = nullptr;
     b->stage_arena_at = b->stage_cap = b->stage_used = 0;
@@ -1998,6 +2030,19 @@ lamehip_batch_destroy(lamehip_batch * b)
         (void) hipFree(b->d_bytes);
     if (b->d_pcmf)
         (void) hipFree(b->d_pcmf);
+    if (b->d_rs_bank)
+        (void) hipFree(b->d_rs_bank);
+    if (b->d_rs_trunk)
+        (void) hipFree(b->d_rs_trunk);
+    if (b->d_rs_tails)
+        (void) hipFree(b->d_rs_tails);
+    if (b->d_rs_streams)
+        (void) hipFree(b->d_rs_streams);
+    if (b->ev_rs[0])
+        (void) hipEventDestroy(b->ev_rs[0]);
+    if (b->ev_rs[1])
+        (void) hipEventDestroy(b->ev_rs[1]);
+    lh_rs_trunk_free(&b->trunk);
     if (b->mid.frames)
         (void) hipFree(b->mid.frames);
     if (b->ev_wait)
@@ -2046,11 +2091,69 @@ lamehip_batch_destroy(lamehip_batch * b)
     delete  b;
 }
 
+/* Device conversion: stream s will be n input samples long.  The host plans -- the trunk grows to the stream's full
+ * chunks, the stream's own last blocks are kept with it -- and with that knows the converted length, the frame count
+ * and the end padding; the samples are not looked at. */
+static int
+batch_plan_stream(lamehip_batch * b, int s, long n)
+{
+    int const fs = fs_of(b->cfg);
+    std::vector < LhRsBlock > &tail = b->tail[(size_t) s];
+    long    conv = 0;
+    int     frames = 0, padding = 0, ntail;
+    if (lh_rs_trunk_extend(b->rs, &b->trunk, n / fs) != 0) {
+        snprintf(g_err, sizeof(g_err), "out of memory (conversion plan)");
+        return -2;
+    }
+    tail.resize(16);
+    ntail = lh_rs_plan_tail(b->rs, &b->trunk, n, tail.data(), (int) tail.size(), &conv, &frames, &padding);
+    if (ntail > (int) tail.size()) {
+        tail.resize((size_t) ntail);
+        ntail = lh_rs_plan_tail(b->rs, &b->trunk, n, tail.data(), (int) tail.size(), &conv, &frames, &padding);
+    }
+    if (ntail < 0)
+        return -1;
+    tail.resize((size_t) ntail);
+    if (conv > b->capf) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_pcm: converted stream (%ld samples) exceeds the pool", conv);
+        return -1;
+    }
+    /* (the kernel stages a block's span of input in LDS: nothing the converter cuts is longer than LH_RS_SPAN_MAX, a
+     * block being at most 1152 input samples and the taps before them; checked all the same, before anything runs) */
+    for (const LhRsBlock & k:tail) {
+        if (k.made > 0 && lh_rs_locate(b->rs->ratio, b->rs->taps, b->rs->phases, k.start, k.made - 1).first + b->rs->taps + 1
+            - lh_rs_locate(b->rs->ratio, b->rs->taps, b->rs->phases, k.start, 0).first > LH_RS_SPAN_MAX) {
+            snprintf(g_err, sizeof(g_err), "conversion plan: a block spans more input than the device kernel stages");
+            return -1;
+        }
+    }
+    b->len_in[(size_t) s] = n;
+    b->len[(size_t) s] = conv;
+    b->nframes[(size_t) s] = frames;
+    b->padding[(size_t) s] = padding;
+    b->rs_dirty[(size_t) s] = 1;
+    return 0;
+}
+
+/* input samples of stream s in the s16 pool */
+static long
+batch_len_in(const lamehip_batch * b, int s)
+{
+    return b->dev_rs ? b->len_in[(size_t) s] : b->len[(size_t) s];
+}
+
 extern "C" int
 lamehip_batch_set_length(lamehip_batch * b, int s, long n)
 {
-    if (!b || s < 0 || s >= b->B || n < 0 || n > b->cap || b->rate_in)
-        return -1;              /* (a converting batch needs the samples themselves: lamehip_batch_set_pcm) */
+    if (!b || s < 0 || s >= b->B || n < 0 || (n > b->cap && !b->dev_rs) || (b->rate_in && !b->dev_rs))
+        return -1;              /* (a batch that converts on the host needs the samples themselves: lamehip_batch_set_pcm) */
+    if (b->dev_rs && n > b->cap) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_length: stream of %ld samples exceeds the pool (%ld per stream)", n, b->cap);
+        return -1;
+    }
+    b->pcm_given = 1;
+    if (b->dev_rs)
+        return batch_plan_stream(b, s, n);
     b->len[(size_t) s] = n;
     b->nframes[(size_t) s] = lh_total_frames_fs(n, fs_of(b->cfg));
     return 0;
@@ -2062,74 +2165,33 @@ lamehip_batch_set_length(lamehip_batch * b, int s, long n)
 static int
 batch_convert_stream(lamehip_batch * b, int s, const short *l, const short *r, long n)
 {
-    std::vector < float >ol, orr;
-    float   il[1152], ir[1152], blk[2][1152];
-    double const ratio = (double) b->rate_in / (double) b->cfg.samplerate;
-    long    fed = 0, mf_size = LH_MF_START;
-    int     frames = 0, owed, padding, frames_left;
-    float const m00 = b->cfg.pcm_scale, m01 = b->cfg.pcm_mix, m10 = 0.0f * b->cfg.pcm_scale, m11 = b->cfg.pcm_scale_r;
-    auto    feed =[&](int m) {
-        int     at = 0;
-        while (m > 0) {
-            int     used = 0, made = 0;
-            for (int ch = 0; ch < b->cfg.channels; ch++)
-                made = lh_rs_block(b->rs, ch, blk[ch], fs_of(b->cfg), (ch ? ir : il) + at, m, &used);
-            if (b->cfg.channels == 1)
-                memset(blk[1], 0, sizeof(blk[1]));
-            ol.insert(ol.end(), blk[0], blk[0] + made);
-            orr.insert(orr.end(), blk[1], blk[1] + made);
-            fed += made;
-            mf_size += made;
-            if (mf_size >= mfn_of(b->cfg)) {
-                frames++;
-                mf_size -= fs_of(b->cfg);
-            }
-            at += used;
-            m -= used;
-        }
-    };
-    lh_rs_init(b->rs, b->rate_in, b->cfg.samplerate);
-    ol.reserve((size_t) ((double) n / ratio) + 4096);
-    orr.reserve((size_t) ((double) n / ratio) + 4096);
-    for (long pos = 0; pos < n; pos += fs_of(b->cfg)) {
-        int const m = (n - pos) > fs_of(b->cfg) ? fs_of(b->cfg) : (int) (n - pos);
-        for (int i = 0; i < m; i++) {
-            float const xl = (float) l[pos + i], xr = (float) r[pos + i];
-            il[i] = xl * m00 + xr * m01;
-            ir[i] = xl * m10 + xr * m11;
-        }
-        feed(m);
+    float  *ol = nullptr, *orr = nullptr;
+    long    conv = 0;
+    int     frames = 0, padding = 0;
+    if (lh_rs_convert_stream(b->rs, b->rate_in, b->cfg.samplerate, fs_of(b->cfg), mfn_of(b->cfg), b->cfg.channels, b->cfg.pcm_scale,
+                             b->cfg.pcm_mix, b->cfg.pcm_scale_r, l, r, n, &ol, &orr, &conv, &frames, &padding) != 0) {
+        snprintf(g_err, sizeof(g_err), "out of memory (sample rate converter)");
+        return -2;
     }
-    owed = (int) (576 + fed - (long) fs_of(b->cfg) * frames);
-    owed += 16. / ratio;
-    padding = fs_of(b->cfg) - (owed % fs_of(b->cfg));
-    if (padding < 576)
-        padding += fs_of(b->cfg);
-    frames_left = (owed + padding) / fs_of(b->cfg);
-    memset(il, 0, sizeof(il));
-    memset(ir, 0, sizeof(ir));
-    while (frames_left > 0) {
-        int const before = frames;
-        int     bunch = (int) (mfn_of(b->cfg) - mf_size);
-        bunch *= ratio;
-        if (bunch > 1152)
-            bunch = 1152;
-        if (bunch < 1)
-            bunch = 1;
-        feed(bunch);
-        frames_left -= (frames != before) ? 1 : 0;
-    }
-    if ((long) ol.size() > b->capf) {
-        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_pcm: converted stream (%ld samples) exceeds the pool", (long) ol.size());
+    if (conv > b->capf) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_pcm: converted stream (%ld samples) exceeds the pool", conv);
+        lh_rs_free(ol);
+        lh_rs_free(orr);
         return -1;
     }
-    b->len[(size_t) s] = (long) ol.size();
+    b->len[(size_t) s] = conv;
     b->nframes[(size_t) s] = frames;
     b->padding[(size_t) s] = padding;
-    if (!ol.empty()) {
-        HIPCHK(hipMemcpy(b->d_pcmf + ((size_t) s * 2) * (size_t) b->capf, ol.data(), ol.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(b->d_pcmf + ((size_t) s * 2 + 1) * (size_t) b->capf, orr.data(), orr.size() * sizeof(float), hipMemcpyHostToDevice));
+    hipError_t e = hipSuccess;
+    if (conv > 0) {
+        e = hipMemcpy(b->d_pcmf + ((size_t) s * 2) * (size_t) b->capf, ol, (size_t) conv * sizeof(float), hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = hipMemcpy(b->d_pcmf + ((size_t) s * 2 + 1) * (size_t) b->capf, orr, (size_t) conv * sizeof(float), hipMemcpyHostToDevice);
     }
+    lh_rs_free(ol);
+    lh_rs_free(orr);
+    if (e != hipSuccess)
+        return set_err("hipMemcpy", e);
     return 0;
 }
 
@@ -2140,7 +2202,7 @@ extern "C" short *lamehip_batch_pcm_host_ptr(lamehip_batch * b);
 static int16_t *
 batch_host_pool(lamehip_batch * b)
 {
-    if (!b->h_pcm && !b->rate_in) {
+    if (!b->h_pcm && (!b->rate_in || b->dev_rs)) {
         const char *e = getenv("LAMEHIP_PINNED_MAX_MB");
         double const limit = (e ? atof(e) : 4096.0) * 1048576.0;
         if ((double) b->B * 4.0 * (double) b->cap > limit)
@@ -2166,9 +2228,10 @@ extern "C" int
 lamehip_batch_set_pcm(lamehip_batch * b, int s, const short *l, const short *r, long n)
 {
     LhDeviceScope const on_device(b ? b->device : -1);
-    if (b && b->rate_in) {
+    if (b && b->rate_in && !b->dev_rs) {
         if (s < 0 || s >= b->B || n < 0)
             return -1;
+        b->pcm_given = 1;
         if (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f)
             r = l;
         return batch_convert_stream(b, s, l, r, n);
@@ -2205,7 +2268,7 @@ lamehip_batch_pcm_host_ptr(lamehip_batch * b)
     LhDeviceScope const on_device(b ? b->device : -1);
     if (!b)
         return nullptr;
-    if (!b->h_pcm && !b->rate_in
+    if (!b->h_pcm && (!b->rate_in || b->dev_rs)
         && hipHostMalloc((void **) &b->h_pcm, (size_t) b->B * 2 * (size_t) b->cap * 2, 0) != hipSuccess) {
         b->h_pcm = nullptr;
         (void) hipGetLastError();
@@ -2215,6 +2278,8 @@ lamehip_batch_pcm_host_ptr(lamehip_batch * b)
      * an asynchronous lamehip_batch_upload / _encode has taken.) */
     if (b->h_pcm && batch_mirror_quiesce(b) != 0)
         return nullptr;
+    if (b->h_pcm)
+        b->pcm_given = 1;
     return b->h_pcm;
 }
 
@@ -2224,6 +2289,8 @@ lamehip_batch_mark_pcm(lamehip_batch * b, int s)
 {
     if (!b || s < 0 || s >= b->B || !b->h_pcm)
         return -1;
+    if (b->dev_rs)
+        b->rs_dirty[(size_t) s] = 1;    /* new samples: the stream is converted again */
     if (!b->row_dirty[(size_t) s]) {
         b->row_dirty[(size_t) s] = 1;
         b->n_dirty++;
@@ -2263,12 +2330,12 @@ lamehip_batch_upload(lamehip_batch * b)
     {
         long long used = 0;
         for (int s = 0; s < b->B; s++)
-            used += b->len[(size_t) s];
+            used += batch_len_in(b, s);
         if (b->n_dirty == b->B && used * 10 >= (long long) b->B * b->cap * 9)
             HIPCHK(hipMemcpyAsync(b->d_pcm, b->h_pcm, (size_t) b->B * 2 * (size_t) b->cap * 2, hipMemcpyHostToDevice, b->up_stream));
         else
             for (int s = 0; s < b->B; s++) {
-                size_t const n = (size_t) b->len[(size_t) s] * 2;
+                size_t const n = (size_t) batch_len_in(b, s) * 2;
                 if (!b->row_dirty[(size_t) s] || n == 0)
                     continue;
                 for (int ch = 0; ch < 2; ch++) {
@@ -2309,7 +2376,7 @@ lamehip_batch_set_pcm_device(lamehip_batch * b, int s, const void *dl, const voi
 extern "C" void *
 lamehip_batch_pcm_device_ptr(lamehip_batch * b)
 {
-    return (b && !b->rate_in) ? (void *) b->d_pcm : nullptr;
+    return (b && (!b->rate_in || b->dev_rs)) ? (void *) b->d_pcm : nullptr;
 }
 
 
@@ -2646,6 +2713,83 @@ lamehip_batch_reset(lamehip_batch * b)
     return batch_reset_states(b);
 }
 
+/* The streams declared since their last conversion go through the device converter, on the batch's stream: the plan
+ * travels first (the trunk only as far as it has grown since the last time), then one launch. */
+static int
+batch_convert_launch(lamehip_batch * b)
+{
+    int     max_blocks = 0;
+    b->rs_ran = 0;
+    b->h_tails.clear();
+    b->h_rs_streams.clear();
+    for (int s = 0; s < b->B; s++) {
+        if (!b->rs_dirty[(size_t) s])
+            continue;
+        LhRsStream d;
+        d.n = b->len_in[(size_t) s];
+        d.stream = s;
+        d.ntrunk = b->trunk.after[d.n / b->trunk.fs].nblk;
+        d.tail_at = (int) b->h_tails.size();
+        d.ntail = (int) b->tail[(size_t) s].size();
+        b->h_tails.insert(b->h_tails.end(), b->tail[(size_t) s].begin(), b->tail[(size_t) s].end());
+        b->h_rs_streams.push_back(d);
+        if (d.ntrunk + d.ntail > max_blocks)
+            max_blocks = d.ntrunk + d.ntail;
+    }
+    if (b->h_rs_streams.empty())
+        return 0;
+    long const ntrunk = b->trunk.after[b->trunk.nchunks].nblk;
+    if (ntrunk > b->rs_trunk_cap) {
+        LhRsBlock *bigger = nullptr;
+        HIPCHK(hipMalloc((void **) &bigger, (size_t) (2 * ntrunk) * sizeof(LhRsBlock)));
+        /* (a conversion of the previous round may still be reading the old one) */
+        HIPCHK(hipStreamSynchronize(b->stream));
+        if (b->d_rs_trunk)
+            (void) hipFree(b->d_rs_trunk);
+        b->d_rs_trunk = bigger;
+        b->rs_trunk_cap = 2 * ntrunk;
+        b->rs_trunk_up = 0;
+    }
+    if (ntrunk > b->rs_trunk_up) {
+        HIPCHK(hipMemcpyAsync(b->d_rs_trunk + b->rs_trunk_up, b->trunk.blk + b->rs_trunk_up,
+                              (size_t) (ntrunk - b->rs_trunk_up) * sizeof(LhRsBlock), hipMemcpyHostToDevice, b->stream));
+        b->rs_trunk_up = ntrunk;
+    }
+    if ((long) b->h_tails.size() > b->rs_tails_cap) {
+        LhRsBlock *bigger = nullptr;
+        long const want = 2 * (long) b->h_tails.size() + 64;
+        HIPCHK(hipMalloc((void **) &bigger, (size_t) want * sizeof(LhRsBlock)));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        if (b->d_rs_tails)
+            (void) hipFree(b->d_rs_tails);
+        b->d_rs_tails = bigger;
+        b->rs_tails_cap = want;
+    }
+    if (!b->h_tails.empty())
+        HIPCHK(hipMemcpyAsync(b->d_rs_tails, b->h_tails.data(), b->h_tails.size() * sizeof(LhRsBlock), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemcpyAsync(b->d_rs_streams, b->h_rs_streams.data(), b->h_rs_streams.size() * sizeof(LhRsStream), hipMemcpyHostToDevice,
+                          b->stream));
+    LhRsParams p;
+    memset(&p, 0, sizeof(p));
+    p.ratio = b->rs->ratio;
+    p.m = lh_rs_matrix(b->cfg.pcm_scale, b->cfg.pcm_mix, b->cfg.pcm_scale_r);
+    p.taps = b->rs->taps;
+    p.phases = b->rs->phases;
+    p.channels = b->cfg.channels;
+    p.one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
+    p.cap_in = b->cap;
+    p.cap_out = b->capf;
+    HIPCHK(hipEventRecord(b->ev_rs[0], b->stream));
+    int const rc = lh_launch_resample(&p, b->d_rs_bank, b->d_rs_trunk, b->d_rs_tails, b->d_rs_streams, (int) b->h_rs_streams.size(),
+                                      max_blocks, b->d_pcm, b->d_pcmf, (void *) b->stream);
+    if (rc)
+        return set_err("conversion launch", (hipError_t) rc);
+    HIPCHK(hipEventRecord(b->ev_rs[1], b->stream));
+    b->rs_ran = 1;
+    b->rs_dirty.assign((size_t) b->B, 0);
+    return 0;
+}
+
 extern "C" int
 lamehip_batch_encode(lamehip_batch * b)
 {
@@ -2715,6 +2859,12 @@ lamehip_batch_encode(lamehip_batch * b)
     }
     HIPCHK(hipMemcpyAsync(b->d_desc, b->h_desc.data(), (size_t) b->B * sizeof(LhStreamDesc),
                           hipMemcpyHostToDevice, b->stream));
+    /* device conversion: behind the upload wait, in front of the analysis kernels */
+    if (b->dev_rs) {
+        int const rc = batch_convert_launch(b);
+        if (rc)
+            return rc;
+    }
     /* (what the launch will be -- and the pool it needs -- before the device's launch order is taken: an allocation of tens
      * of GB must not keep other batches' launches waiting) */
     LhLaunchPlan plan;
@@ -2835,6 +2985,110 @@ lamehip_batch_set_device_packing(lamehip_batch * b, int on)
         return -1;
     b->dev_pack = on != 0;
     return 0;
+}
+
+/* Device rate conversion (a batch whose input rate differs from the encoder's): the input stays s16, in a pool at the
+ * input rate that takes PCM the way a batch without conversion does -- pinned mirror, device-resident input --, and
+ * lamehip_batch_encode converts it into the float pool with a kernel (lh_resample_dev.hip) in front of the analysis
+ * kernels.  Only before any PCM is handed over; off (the default): lamehip_batch_set_pcm converts on the host. */
+extern "C" int
+lamehip_batch_set_device_resampling(lamehip_batch * b, int on)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b)
+        return -1;
+    if (!b->rate_in) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_device_resampling: this batch does not convert (input rate = output rate)");
+        return -1;
+    }
+    if (b->pcm_given || b->encoded || b->incremental) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_device_resampling: only before any PCM is handed over");
+        return -1;
+    }
+    if (!on || b->dev_rs) {
+        b->dev_rs = on != 0 && b->dev_rs;
+        return 0;
+    }
+    /* everything new first: a failure leaves the batch as it was */
+    lh_rs_init(b->rs, b->rate_in, b->cfg.samplerate);
+    int const rows = 2 * b->rs->phases + 1;
+    size_t const pool = (size_t) b->B * 2 * (size_t) b->cap * sizeof(int16_t);
+    int16_t *pcm = nullptr;
+    float  *bank = nullptr;
+    LhRsStream *streams = nullptr;
+    hipEvent_t ev[2] = { nullptr, nullptr };
+    std::vector < float >h_bank((size_t) rows * LH_RS_ROW, 0.0f);
+    for (int k = 0; k < rows; k++)
+        memcpy(&h_bank[(size_t) k * LH_RS_ROW], b->rs->bank[k], (size_t) (b->rs->taps + 1) * sizeof(float));
+    hipError_t e = hipMalloc((void **) &pcm, pool);
+    if (e == hipSuccess)
+        e = hipMalloc((void **) &bank, h_bank.size() * sizeof(float));
+    if (e == hipSuccess)
+        e = hipMalloc((void **) &streams, (size_t) b->B * sizeof(LhRsStream));
+    if (e == hipSuccess)
+        e = hipEventCreate(&ev[0]);
+    if (e == hipSuccess)
+        e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess)
+        e = hipMemset(pcm, 0, pool);
+    if (e == hipSuccess)
+        e = hipMemcpy(bank, h_bank.data(), h_bank.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        if (pcm)
+            (void) hipFree(pcm);
+        if (bank)
+            (void) hipFree(bank);
+        if (streams)
+            (void) hipFree(streams);
+        if (ev[0])
+            (void) hipEventDestroy(ev[0]);
+        if (ev[1])
+            (void) hipEventDestroy(ev[1]);
+        return set_err("lamehip_batch_set_device_resampling: device allocation", e);
+    }
+    (void) hipFree(b->d_pcm);   /* (the one-sample placeholder of a batch that converts on the host) */
+    b->d_pcm = pcm;
+    b->d_rs_bank = bank;
+    b->d_rs_streams = streams;
+    b->ev_rs[0] = ev[0];
+    b->ev_rs[1] = ev[1];
+    lh_rs_trunk_init(&b->trunk, fs_of(b->cfg), mfn_of(b->cfg));
+    b->len_in.assign((size_t) b->B, 0);
+    b->tail.assign((size_t) b->B, std::vector < LhRsBlock > ());
+    b->rs_dirty.assign((size_t) b->B, 0);
+    b->dev_rs = 1;
+    return 0;
+}
+
+/* test accessor: the converted signal of stream s as the encoder reads it (after lamehip_batch_set_pcm when the host
+ * converts, after lamehip_batch_encode when the device does); returns its length, or a negative code */
+extern "C" long
+lamehip_batch_get_converted(lamehip_batch * b, int s, float *l, float *r, long cap)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b || s < 0 || s >= b->B || !b->rate_in || !l || !r)
+        return -1;
+    if (b->dev_rs && b->rs_dirty[(size_t) s]) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_get_converted: stream %d has not been converted yet (lamehip_batch_encode)", s);
+        return -1;
+    }
+    long const n = b->len[(size_t) s];
+    if (n > cap)
+        return -1;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (n > 0) {
+        HIPCHK(hipMemcpy(l, b->d_pcmf + ((size_t) s * 2) * (size_t) b->capf, (size_t) n * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(r, b->d_pcmf + ((size_t) s * 2 + 1) * (size_t) b->capf, (size_t) n * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return n;
+}
+
+/* HIP-event time of the device conversion of the last lamehip_batch_encode (after lamehip_batch_sync); 0 when none ran */
+extern "C" float
+lamehip_batch_last_resample_ms(lamehip_batch * b)
+{
+    return b ? b->rs_ms : 0.0f;
 }
 
 /* bytes of one stream as the device packed them (audio frames incl. the final padding, no tag) */
@@ -2992,6 +3246,11 @@ lamehip_batch_sync(lamehip_batch * b)
     HIPCHK(hipStreamSynchronize(b->stream));
     if (b->encoded) {
         float   ms = 0;
+        b->rs_ms = 0;
+        if (b->rs_ran && hipEventElapsedTime(&b->rs_ms, b->ev_rs[0], b->ev_rs[1]) != hipSuccess) {
+            (void) hipGetLastError();
+            b->rs_ms = 0;
+        }
         if (hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess)
             b->last_ms = ms;
         b->part_ms[0] = b->part_ms[1] = b->part_ms[2] = 0;

@@ -5,6 +5,7 @@
 #define LH_HOST_H
 
 #include "lamehip_types.h"
+#include "lh_rs_sample.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -159,6 +160,50 @@ typedef struct LhResampler {
 int     lh_rs_needed(int rate_in, int rate_out);
 void    lh_rs_init(LhResampler * r, int rate_in, int rate_out);
 int     lh_rs_block(LhResampler * r, int ch, float *out, int want, const float *in, int len, int *used);
+
+/* A whole stream the way a batch converts it (lh_resample.c): the float planes (malloc'ed; lh_rs_free), the
+ * converted length, the frame count and the end padding.  fs / mfn: samples per frame and the samples that
+ * have to be buffered before a frame can be encoded. */
+int     lh_rs_convert_stream(LhResampler * r, int rate_in, int rate_out, int fs, int mfn, int channels, float pcm_scale,
+                             float pcm_mix, float pcm_scale_r, const short *l, const short *rr, long n, float **out_l,
+                             float **out_r, long *conv_len, int *frames, int *padding);
+void    lh_rs_free(void *p);
+
+/* The same conversion as a plan: the blocks it consists of, without looking at a sample.  The blocks of a
+ * stream's full chunks (fs input samples each) are those of every stream with as many chunks -- the trunk,
+ * kept once and grown on demand --; its last partial chunk and the flush are the stream's own tail. */
+typedef struct LhRsCursor {
+    double  clock;
+    long long in_at;            /* input samples consumed */
+    long long fed;              /* output samples made */
+    long    mf_size;
+    int     frames;
+    int     nblk;               /* blocks so far */
+} LhRsCursor;
+
+typedef struct LhRsTrunk {
+    int     fs, mfn;
+    long    nchunks;            /* chunks planned: after[0 .. nchunks] are valid */
+    long    cap_chunks;
+    LhRsCursor *after;          /* after[c]: the converter behind c full chunks; after[c].nblk trunk blocks lead there */
+    LhRsBlock *blk;
+    long    cap_blk;
+} LhRsTrunk;
+
+void    lh_rs_trunk_init(LhRsTrunk * t, int fs, int mfn);
+void    lh_rs_trunk_free(LhRsTrunk * t);
+int     lh_rs_trunk_extend(const LhResampler * r, LhRsTrunk * t, long nchunks);
+/* the tail of a stream of n input samples behind trunk block after[n / fs].nblk (the trunk must reach that far);
+ * returns the number of tail blocks -- only the first `cap' are written -- or -1 */
+int     lh_rs_plan_tail(const LhResampler * r, const LhRsTrunk * t, long n, LhRsBlock * tail, int cap, long *conv_len,
+                        int *frames, int *padding);
+/* trunk prefix and tail of one stream in one list (at most `cap' written); *ntrunk = length of the prefix */
+int     lh_rs_plan(const LhResampler * r, int fs, int mfn, long n, LhRsBlock * out, int cap, int *ntrunk, long *conv_len,
+                   int *frames, int *padding);
+/* one block of a plan evaluated on the host, sample by sample as the device kernel does it: writes
+ * out_l / out_r [out_at, out_at + made) */
+void    lh_rs_eval_block(const LhResampler * r, const LhRsBlock * b, int channels, float pcm_scale, float pcm_mix,
+                         float pcm_scale_r, const short *l, const short *rr, long n, float *out_l, float *out_r);
 
 /* ---- ReplayGain "radio gain" for the LAME tag (lh_replaygain.c; reference gain_analysis.c) ---- */
 #define LH_RG_BINS 12000        /* 0.01 dB steps up to 120 dB */

@@ -1,0 +1,149 @@
+/*
+ * lh_resample_dev.hip -- the rate converter of a batch on the device (gfx950): fills the batch's float pool
+ * from its s16 pool, bit for bit what lh_rs_block (lh_resample.c) makes of the same samples.
+ *
+ * The converter's serial part -- which blocks there are, and the clock each starts at -- is a plan the host
+ * makes from the stream lengths alone (lh_rs_plan_tail / lh_rs_trunk_extend).  Given its block an output
+ * sample depends on nothing but the stream's input: one workgroup per (stream, block) stages the span of input
+ * the block's outputs touch, behind the PCM matrix and as float, in LDS -- zeros for positions before the
+ * stream and from its length on, which are never read from memory --, then every lane locates its outputs
+ * (lh_rs_locate) and takes the ordered dot products (lh_rs_sample.h: the host's own text) for both channels.
+ * The located kernel is looked up once for the two channels.
+ *
+ * The bank of kernels is read through the vector cache, rows of LH_RS_ROW floats fetched 16 bytes at a time (a
+ * copy of the bank in LDS, loaded once per workgroup for a run of blocks, measured 2.5 times slower: DESIGN.md).
+ * Built with -ffp-contract=off like every object of the library.
+ */
+#include <stdint.h>
+#include <math.h>
+
+#ifdef LH_EMU
+#include "hipemu.h"
+#define LH_RS_FN static inline
+#else
+#include <hip/hip_runtime.h>
+#define LH_RS_DEVICE
+#define LH_RS_FN static __device__ __forceinline__
+#endif
+#include "lh_rs_sample.h"
+
+#define LH_RS_NT 256
+
+struct alignas(16) LhRsF4 {
+    float   v[4];
+};
+
+template < int TAPS > LH_RS_FN void
+rs_convert_block(const LhRsParams & p, const float *bank, const LhRsBlock & blk, long long n,
+                 const int16_t * in_l, const int16_t * in_r, float *out_l, float *out_r, float (*xs)[LH_RS_SPAN_MAX])
+{
+    int const tid = (int) threadIdx.x;
+    if (blk.made <= 0)
+        return;
+    /* the span of input the block touches, from the first tap of its first output to the last of its last */
+    int const lo = lh_rs_locate(p.ratio, TAPS, p.phases, blk.start, 0).first;
+    int const count = lh_rs_locate(p.ratio, TAPS, p.phases, blk.start, blk.made - 1).first + TAPS + 1 - lo;
+    if (count > LH_RS_SPAN_MAX)
+        return;                 /* (no plan of the host's has such a block: lamehip_batch_set_length refuses it) */
+    for (int t = tid; t < count; t += LH_RS_NT) {
+        long long const at = blk.in_at + lo + t;
+        float   xl = 0.0f, xr = 0.0f;
+        if (at >= 0 && at < n) {
+            float const sl = (float) in_l[at], sr = p.one_plane ? sl : (float) in_r[at];
+            xl = lh_rs_mix(sl, sr, p.m.m00, p.m.m01);
+            xr = lh_rs_mix(sl, sr, p.m.m10, p.m.m11);
+        }
+        xs[0][t] = xl;
+        xs[1][t] = xr;
+    }
+    __syncthreads();
+    for (int k = tid; k < blk.made; k += LH_RS_NT) {
+        LhRsSpot const s = lh_rs_locate(p.ratio, TAPS, p.phases, blk.start, k);
+        const float *x0 = xs[0] + (s.first - lo), *x1 = xs[1] + (s.first - lo);
+        float   a0 = 0.f, a1 = 0.f;
+        const LhRsF4 *row = (const LhRsF4 *) (bank + (size_t) s.kernel * LH_RS_ROW);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            LhRsF4 const w = row[q];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                a0 = LH_RS_FADD(a0, LH_RS_FMUL(x0[4 * q + j], w.v[j]));
+                a1 = LH_RS_FADD(a1, LH_RS_FMUL(x1[4 * q + j], w.v[j]));
+            }
+        }
+        if (TAPS == 32) {
+            float const w = bank[(size_t) s.kernel * LH_RS_ROW + 32];
+            a0 = LH_RS_FADD(a0, LH_RS_FMUL(x0[32], w));
+            a1 = LH_RS_FADD(a1, LH_RS_FMUL(x1[32], w));
+        }
+        out_l[blk.out_at + k] = a0;
+        out_r[blk.out_at + k] = p.channels == 1 ? 0.0f : a1;
+    }
+}
+
+/* grid: x = block of the stream, y = entry of `streams' */
+template < int TAPS >
+#ifndef LH_EMU
+__global__ void __launch_bounds__(LH_RS_NT)
+#else
+void
+#endif
+lh_resample_kernel(LhRsParams p, const float *bank, const LhRsBlock * trunk, const LhRsBlock * tails, const LhRsStream * streams,
+                   const int16_t * pcm, float *pcmf)
+{
+    __shared__ float xs[2][LH_RS_SPAN_MAX];
+    LhRsStream const sd = streams[blockIdx.y];
+    int const j = (int) blockIdx.x;
+    if (j >= sd.ntrunk + sd.ntail)
+        return;
+    LhRsBlock const blk = j < sd.ntrunk ? trunk[j] : tails[sd.tail_at + (j - sd.ntrunk)];
+    const int16_t *in_l = pcm + (size_t) sd.stream * 2 * (size_t) p.cap_in, *in_r = in_l + p.cap_in;
+    float  *out_l = pcmf + (size_t) sd.stream * 2 * (size_t) p.cap_out, *out_r = out_l + p.cap_out;
+    rs_convert_block < TAPS > (p, bank, blk, sd.n, in_l, in_r, out_l, out_r, xs);
+}
+
+#ifndef LH_EMU
+/* nstreams entries of `streams', the longest with max_blocks blocks.  Returns a hipError_t. */
+extern "C" int
+lh_launch_resample(const LhRsParams * p, const float *bank, const LhRsBlock * trunk, const LhRsBlock * tails,
+                   const LhRsStream * streams, int nstreams, int max_blocks, const int16_t * pcm, float *pcmf, void *stream)
+{
+    if (nstreams <= 0 || max_blocks <= 0)
+        return 0;
+    if ((p->taps != 31 && p->taps != 32) || p->phases < 1 || p->phases > 320)
+        return (int) hipErrorInvalidValue;
+    /* (blockIdx.y ends at 65535: a longer list goes in slices) */
+    for (int at = 0; at < nstreams; at += 65535) {
+        int const ns = nstreams - at < 65535 ? nstreams - at : 65535;
+        dim3 const grid((unsigned) max_blocks, (unsigned) ns), block(LH_RS_NT);
+        if (p->taps == 31)
+            hipLaunchKernelGGL((lh_resample_kernel < 31 >), grid, block, 0, (hipStream_t) stream, *p, bank, trunk, tails, streams + at,
+                               pcm, pcmf);
+        else
+            hipLaunchKernelGGL((lh_resample_kernel < 32 >), grid, block, 0, (hipStream_t) stream, *p, bank, trunk, tails, streams + at,
+                               pcm, pcmf);
+        hipError_t const e = hipGetLastError();
+        if (e != hipSuccess)
+            return (int) e;
+    }
+    return 0;
+}
+#else
+extern "C" int
+lh_emu_resample(const LhRsParams * params, const float *bank, const LhRsBlock * trunk, const LhRsBlock * tails,
+                const LhRsStream * streams, int nstreams, int max_blocks, const int16_t * pcm, float *pcmf)
+{
+    LhRsParams const p = *params;
+    hipemu_dim3 grid = { (unsigned) max_blocks, (unsigned) nstreams, 1 }, block = { LH_RS_NT, 1, 1 };
+    if (nstreams <= 0 || max_blocks <= 0)
+        return 0;
+    hipemu_run(grid, block,[=] () {
+               if (p.taps == 31)
+                   lh_resample_kernel < 31 > (p, bank, trunk, tails, streams, pcm, pcmf);
+               else
+                   lh_resample_kernel < 32 > (p, bank, trunk, tails, streams, pcm, pcmf);
+               }
+    );
+    return 0;
+}
+#endif

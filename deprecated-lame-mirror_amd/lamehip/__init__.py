@@ -238,6 +238,32 @@ class Batch:
         self.lib.lamehip_batch_set_device_packing.argtypes = [C.c_void_p, C.c_int]
         assert self.lib.lamehip_batch_set_device_packing(self.b, 1 if on else 0) == 0
 
+    def set_device_resampling(self, on=True):
+        """A batch whose input rate differs from the encoder's: convert on the device (inside encode()) instead of
+        on the host (inside set_pcm()); opens set_pcm_device / pcm_device_ptr / set_length / pcm_host for it.
+        Before any PCM is handed over."""
+        self.lib.lamehip_batch_set_device_resampling.argtypes = [C.c_void_p, C.c_int]
+        rc = self.lib.lamehip_batch_set_device_resampling(self.b, 1 if on else 0)
+        if rc:
+            raise RuntimeError("lamehip_batch_set_device_resampling failed (%d): %s" % (rc, last_error()))
+
+    def converted(self, s):
+        """The converted signal of stream s as the encoder reads it: float32 [2, converted length] (test accessor)."""
+        self.lib.lamehip_batch_get_converted.restype = C.c_long
+        self.lib.lamehip_batch_get_converted.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
+        cap = (self.frames(s) + 4) * 1152
+        out = np.zeros((2, cap), dtype=np.float32)
+        n = self.lib.lamehip_batch_get_converted(self.b, s, out[0].ctypes.data, out[1].ctypes.data, cap)
+        if n < 0:
+            raise RuntimeError("lamehip_batch_get_converted failed (%d): %s" % (n, last_error()))
+        return out[:, :n].copy()
+
+    def resample_ms(self):
+        """HIP-event time of the last encode()'s device conversion, 0 when none ran."""
+        self.lib.lamehip_batch_last_resample_ms.restype = C.c_float
+        self.lib.lamehip_batch_last_resample_ms.argtypes = [C.c_void_p]
+        return float(self.lib.lamehip_batch_last_resample_ms(self.b))
+
     def get_bytes(self, s):
         self.lib.lamehip_batch_get_bytes.restype = C.c_long
         self.lib.lamehip_batch_get_bytes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long]

@@ -11,7 +11,7 @@
  * of handles.
  *
  * Everything here is plain C: pointers and sizes only, no torch / HIP types.
- * Unsupported settings (MPEG-2 / 2.5 output rates, free format) make
+ * Unsupported settings (free format) make
  * lame_init_params() return -1 instead of silently taking another path, and
  * every call fails with LAMEHIP_ERR_NODEVICE when no HIP device is present --
  * there is no CPU fallback inside this library.
@@ -49,7 +49,7 @@ int     lame_set_in_samplerate(lame_t, int);                         /* lame.h:1
 int     lame_get_in_samplerate(const lame_t);                        /* lame.h:189 */
 int     lame_set_num_channels(lame_t, int);                          /* lame.h:192 (2, or 1 = mono: only buffer_l is read) */
 int     lame_get_num_channels(const lame_t);                         /* lame.h:193 */
-int     lame_set_out_samplerate(lame_t, int);                        /* lame.h:224 (must equal the input rate) */
+int     lame_set_out_samplerate(lame_t, int);                        /* lame.h:224 (0 = by bitrate; != input rate: converted) */
 int     lame_get_out_samplerate(const lame_t);                       /* lame.h:225 */
 int     lame_set_brate(lame_t, int);                                 /* lame.h:353 */
 int     lame_get_brate(const lame_t);                                /* lame.h:354 */
@@ -226,9 +226,11 @@ lamehip_batch *lamehip_batch_create_on(int device, const lame_t proto, int nstre
 int     lamehip_set_device(lame_t, int device);
 void    lamehip_batch_destroy(lamehip_batch *);
 /* copy one stream's planar s16 PCM host -> HBM (H2D, synchronous).  When proto's input rate differs from
- * its output rate the stream is converted on the host first, exactly as the reference converts it when
- * lame_encode_buffer is fed 1152 input samples per call (util.c:520-697; capacity then counts input
- * samples, and the _device variants below are refused) */
+ * its output rate the stream is converted exactly as the reference converts it when lame_encode_buffer is
+ * fed a frame of input samples per call (util.c:520-697); capacity and lengths then count input samples.
+ * By default this call converts on the host, and the _device variants, lamehip_batch_set_length and the
+ * pinned mirror below are refused: lamehip_batch_set_device_resampling moves the conversion to the device
+ * and opens them. */
 int     lamehip_batch_set_pcm(lamehip_batch *, int stream, const short *l, const short *r, long nsamples);
 /* same, from planar s16 buffers that already live in HBM (D2D) */
 int     lamehip_batch_set_pcm_device(lamehip_batch *, int stream, const void *dev_l, const void *dev_r, long nsamples);
@@ -236,6 +238,25 @@ int     lamehip_batch_set_pcm_device(lamehip_batch *, int stream, const void *de
  * that already lives on the GPU fill it in place (then declare lengths) */
 void   *lamehip_batch_pcm_device_ptr(lamehip_batch *);
 int     lamehip_batch_set_length(lamehip_batch *, int stream, long nsamples);
+/* Rate conversion on the device, for a batch whose input rate differs from its output rate (-1 for any other, and
+ * -1 once PCM, a length or the pinned mirror has been handed over; lamehip_last_error() says which).  Switched on,
+ * the batch keeps its input as s16 at the input rate in a pool [stream][2][capacity], and lamehip_batch_set_pcm,
+ * _set_pcm_device, _pcm_device_ptr, _set_length, _pcm_host_ptr, _mark_pcm and _upload work as on a batch that does
+ * not convert.  Declaring a length plans the conversion on the host without looking at a sample -- converted length,
+ * lamehip_batch_frames and the tag's padding are known at once; -1 when the converted stream exceeds the pool --, and
+ * lamehip_batch_encode converts the streams declared (lamehip_batch_set_pcm* / _set_length / _mark_pcm) since their
+ * last conversion with a kernel on the batch's stream, in front of the analysis kernels.  Samples at or beyond a
+ * stream's length are never read.  Same floats, hence same bytes, as the host conversion.  An allocation failure
+ * returns LAMEHIP_ERR_DEVICE and leaves the batch as it was.  lamehip_batch_append stays refused on a converting
+ * batch either way. */
+int     lamehip_batch_set_device_resampling(lamehip_batch *, int on);
+/* test accessor: the converted signal of a stream (float planes as the encoder reads them), valid after
+ * lamehip_batch_set_pcm when the host converts and after lamehip_batch_encode when the device does; waits for the
+ * batch's stream.  Returns the converted length, or a negative code (-1 also when it exceeds cap). */
+long    lamehip_batch_get_converted(lamehip_batch *, int stream, float *l, float *r, long cap);
+/* HIP-event time in ms of the device conversion of the last lamehip_batch_encode (after lamehip_batch_sync); 0 when
+ * none ran.  It is not part of lamehip_batch_last_kernel_ms / _parts_ms. */
+float   lamehip_batch_last_resample_ms(lamehip_batch *);
 
 /* Incremental use -- lame_encode_buffer (lame.h:715-722, lame.c:1672-1775) for all streams of a batch at once:
  *   lamehip_batch_append            stage n more samples of one stream (host, pinned memory; any n >= 0, ragged
@@ -277,7 +298,8 @@ int     lamehip_batch_get_bytes_all(lamehip_batch *, unsigned char *out, long ou
  * frontend loop lame_encode_buffer -> fwrite, frontend/lame_main.c:449-520, for many streams at once):
  *   lamehip_batch_pcm_host_ptr   pinned mirror of the s16 pool, short[stream][2][capacity]; write the samples there
  *                                (then lamehip_batch_set_length + lamehip_batch_mark_pcm) or let lamehip_batch_set_pcm
- *                                copy them there -- NULL for a batch that converts the sample rate;
+ *                                copy them there -- NULL for a batch that converts the sample rate on the host
+ *                                (lamehip_batch_set_device_resampling);
  *   lamehip_batch_upload         one asynchronous H2D copy of what changed (lamehip_batch_encode does it if pending);
  *   lamehip_batch_fetch          after lamehip_batch_encode of a device-packed batch: bytes and per-stream sizes start
  *                                their way to pinned host memory behind the kernel, asynchronously;
