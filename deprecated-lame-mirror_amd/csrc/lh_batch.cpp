@@ -1,0 +1,1806 @@
+/*
+ * lh_batch.cpp -- the lamehip_batch_* API of liblamehip (declared in include/lamehip.h): many streams with one
+ * set of settings, encoded by one launch of the split pipeline (or of the fused kernel).
+ *
+ * Host side only, like lh_api.cpp, which holds the lame_* handle API; what the two share is in lh_api_int.h.
+ */
+#include <time.h>
+#include <thread>
+#include <atomic>
+
+#include "lh_api_int.h"
+
+/* per device: the end of the last launch that filled it (lamehip_batch_encode) */
+static LhLaunchSerial &
+launch_serial(int device)
+{
+    static LhLaunchSerial per_device[64];
+    return per_device[(device >= 0 && device < 64) ? device : 0];
+}
+
+/* ====================================================================== */
+/* batch extension                                                          */
+
+/* Batches go through the split pipeline unless LAMEHIP_FUSED=1 asks for the single fused kernel (A/B measurements; the
+ * handle API always uses the fused kernel: one frame per launch has nothing to analyse ahead). */
+static int
+batch_use_split(void)
+{
+    const char *e = getenv("LAMEHIP_FUSED");
+    return !(e && e[0] == '1');
+}
+
+/* LAMEHIP_SPLIT_DENY=1, looked at before every launch: this launch takes the fused kernel as if the pools could not be had
+ * (test aid: a batch whose launches change kernels mid-stream, tests/test_gpu_parity.py) */
+static int
+batch_split_denied(void)
+{
+    const char *e = getenv("LAMEHIP_SPLIT_DENY");
+    return e && e[0] == '1';
+}
+
+
+/* (made by lamehip_batch_create_on with `new lamehip_batch()': what has no initialiser below starts zeroed or empty.
+ * Everything HIP is held by an owner, lh_hip_own.h, and goes with `delete' -- inside the batch's LhDeviceScope.) */
+struct lamehip_batch {
+    int     device = 0;
+    LhConfig cfg;
+    LhTables *tab = nullptr;
+    LhDeviceConst dc;
+    int     B = 0;
+    long    cap = 0;
+    LhDevBuf < int16_t > d_pcm; /* [B][2][cap] */
+    LhDevBuf < LhStreamState > d_state;
+    LhDevBuf < LhStreamState > d_state0;        /* the streams' initial states (batch_reset_states) */
+    LhDevBuf < LhStreamDesc > d_desc;
+    LhDevBuf < LhFrameOut > d_out;
+    std::vector < long >len;
+    std::vector < int >nframes;
+    std::vector < long long >out_off;
+    /* device bit packing (lamehip_batch_set_device_packing) */
+    int     dev_pack = 0;
+    LhDevBuf < uint8_t > d_bytes;
+    std::vector < long long >bytes_off;
+    std::vector < LhStreamDesc > h_desc;
+    LhStream stream;
+    LhEvent ev0, ev1;
+    float   last_ms = 0;
+    int     encoded = 0;
+    /* input rate != output rate: set_pcm converts on the host (as the reference's frontend would have
+     * it: lame_encode_buffer calls of 1152 input samples, then the flush) into a float pool */
+    int     rate_in = 0;
+    LhResampler *rs = nullptr;
+    LhDevBuf < float >d_pcmf;   /* [B][2][capf] */
+    long    capf = 0;
+    std::vector < int >padding; /* encoder_padding per stream (tag frame) */
+    /* ... or, after lamehip_batch_set_device_resampling, on the device: the s16 pool d_pcm holds the input ([B][2][cap] at
+     * the input rate, with its pinned mirror and device-side entry points as in a batch that does not convert), the host
+     * only plans (lh_rs_trunk_extend / lh_rs_plan_tail: the blocks all streams share, and each stream's own last blocks) and
+     * lamehip_batch_encode launches lh_resample_dev.hip over the streams declared since their last conversion */
+    int     dev_rs = 0;
+    int     pcm_given = 0;      /* PCM (or a length, or the mirror) has been handed over: the converter's place is settled */
+    LhRsTrunk trunk = {};
+    std::vector < long >len_in; /* input samples per stream (len[] is the converted length) */
+    std::vector < std::vector < LhRsBlock > >tail;
+    std::vector < char >rs_dirty;       /* declared since the stream's last conversion */
+    std::vector < LhRsBlock > h_tails;  /* what the last launch's plan consisted of besides the trunk */
+    std::vector < LhRsStream > h_rs_streams;
+    LhDevBuf < float >d_rs_bank;
+    LhDevBuf < LhRsBlock > d_rs_trunk, d_rs_tails;
+    LhDevBuf < LhRsStream > d_rs_streams;
+    long    rs_trunk_up = 0;    /* blocks of the trunk uploaded so far */
+    LhEvent ev_rs[2];
+    int     rs_ran = 0;         /* the last lamehip_batch_encode converted something (between ev_rs[0] and ev_rs[1]) */
+    float   rs_ms = 0;
+    /* incremental use (lamehip_batch_append ...): samples in the pool / frames encoded per stream, a
+     * packer and the bytes not yet drained per stream, and the pinned staging area of the next
+     * lamehip_batch_encode_available (see h_stage below) */
+    int     incremental = 0;
+    std::vector < long >fed;
+    std::vector < int >done;
+    std::vector < int >staged;
+    std::vector < LhBitstream > packer;
+    std::vector < std::vector < unsigned char > >pending;
+    std::vector < LhFrameOut > last;
+    std::vector < char >have_last;
+    /* pinned / HBM: [B descriptors][LH_STAGE_SEGS x 4 ints: the chunks][arena of staged samples, back to back] */
+    LhPinned < unsigned char >h_stage;
+    LhDevBuf < unsigned char >d_stage;
+    long    stage_arena_at = 0; /* byte offset of the arena */
+    long    stage_cap = 0;      /* samples the arena holds */
+    long    stage_used = 0;     /* samples staged */
+    int     stage_nseg = 0;     /* chunks staged */
+    int     finished = 0;       /* lamehip_batch_finish has run: the streams are closed */
+    std::vector < LhFrameOut > h_new;
+    /* pinned host side of a pipelined batch (lamehip_batch_pcm_host_ptr / _upload / _fetch): the mirror of the
+     * s16 pool the caller (or lamehip_batch_set_pcm) writes, which reaches HBM with one asynchronous copy on
+     * the batch's stream; the device packer's bytes and a two-word summary per stream (bytes, status) on the
+     * way back.  Another batch's copies and kernel run meanwhile (each batch has its own stream). */
+    LhPinned < int16_t > h_pcm;
+    std::vector < char >row_dirty;      /* streams whose mirror rows are newer than the pool */
+    int     n_dirty = 0;
+    LhPinned < unsigned char >h_bytes;
+    LhDevBuf < long long >d_sum;
+    LhPinned < long long >h_sum;
+    int     fetched = 0;        /* the bytes of the last encode are in (or on their way into) h_bytes */
+    /* the copies of a pipelined batch have streams of their own (different hardware queues from the kernel's, and
+     * from each other: an upload queued behind the previous round's download on one stream cost 12 % of the
+     * pipeline's throughput), tied to the kernel's stream by events; made by batch_copy_streams, all five at once */
+    LhStream up_stream, down_stream;
+    LhEvent ev_up, ev_sum, ev_down;
+    int     up_pending = 0, down_pending = 0;
+    int     up_inflight = 0;    /* an H2D copy out of the pinned mirror may still be running (host view: cleared only after ev_up) */
+    int     launched = 0;       /* a kernel was launched on this batch and ev1 recorded (survives lamehip_batch_reset) */
+    /* the split pipeline's pool (one record per frame of a launch, like d_out) and the events between its kernels */
+    LhDevBuf < LhMidFrame > mid;
+    int     split = 0;          /* this batch's launches go through the split pipeline (batch_use_split) */
+    LhEvent ev_part[2];
+    LhEvent ev_wait;            /* behind the launch; only ever polled (hipEventQuery between short sleeps in lamehip_batch_sync): the
+                                 * host thread sleeps instead of spinning on the stream (a rank per GPU must not burn a CPU per rank
+                                 * while its kernel runs) */
+    float   part_ms[3] = { 0, 0, 0 };   /* analysis, sub-band, encode kernel of the last launch (0: fused launch) */
+    int     last_split = 0;
+    /* a launch in windows of frames (batch_plan): the windows' descriptors (host, then HBM: [window][stream]) and three events
+     * per window (its start, behind its analysis kernels, behind its sub-band kernel) */
+    std::vector < LhStreamDesc > h_wdesc;
+    LhDevBuf < LhStreamDesc > d_wdesc;
+    std::vector < LhEvent > ev_win;
+    int     last_windows = 1;   /* sub-launches of the last launch (1: the whole launch at once) */
+};
+
+/* what batch_plan decides about a launch (outside the devices' launch order: it may allocate) and batch_launch carries out */
+struct LhLaunchPlan {
+    long long total;            /* frames of the launch */
+    int     max_frames;         /* of its longest stream */
+    int     split;              /* the split pipeline (else the fused kernel) */
+    int     window;             /* frames per stream and sub-launch; 0: the whole launch at once */
+    int     nwin;
+};
+
+/* room for `need' records in the split pipeline's pool (0), or not (-1: the pool is gone, *free_records says how many would
+ * fit and lamehip_last_error() why) */
+static int
+batch_mid_reserve(lamehip_batch * b, long long need, long long *free_records = nullptr)
+{
+    /* (the encode kernel touches the record BEHIND the one it works on, the launch's last frame included: one spare
+     * record has to exist whatever the launch's total is -- a later launch whose total equals the capacity must not
+     * read past the pool) */
+    if (free_records)
+        *free_records = 0;
+    if (need + 1 <= (long long) b->mid.cap())
+        return 0;
+    size_t  free_b = 0, total_b = 0;
+    long long const want = need + 64;
+    /* (the old pool goes first, unlike LhDevBuf::reserve: what it held counts as free for the new one) */
+    b->mid.release();
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess)
+        free_b = 0;
+    {
+        /* LAMEHIP_MID_BUDGET_MB=n: no more than n MB count as free (test aid: the window size as a device with little
+         * memory left would choose it) */
+        const char *e = getenv("LAMEHIP_MID_BUDGET_MB");
+        long const mb = e ? strtol(e, nullptr, 10) : 0;
+        if (mb > 0 && (size_t) mb * 1000000u < free_b)
+            free_b = (size_t) mb * 1000000u;
+    }
+    if (free_records)
+        *free_records = (long long) (0.8 * (double) free_b / (double) sizeof(LhMidFrame)) - 64;
+    if ((double) want * (double) sizeof(LhMidFrame) > 0.8 * (double) free_b) {
+        /* (not an error: the launch runs in windows or takes the fused kernel; lamehip_last_error() says why) */
+        snprintf(g_err, sizeof(g_err), "split pipeline: %lld frames need %.1f GB of analysis records, %.1f GB free",
+                 need, (double) want * (double) sizeof(LhMidFrame) / 1e9, (double) free_b / 1e9);
+        return -1;
+    }
+    if (b->mid.alloc((size_t) want) != hipSuccess) {
+        (void) hipGetLastError();
+        snprintf(g_err, sizeof(g_err), "split pipeline: hipMalloc of %.1f GB of analysis records failed",
+                 (double) want * (double) sizeof(LhMidFrame) / 1e9);
+        return -1;
+    }
+    return 0;
+}
+
+/* LAMEHIP_MID_WINDOW=n, looked at before every launch: the split pipeline works through a launch in windows of n frames per
+ * stream whatever the memory would allow (tuning / test aid; 0 or unset: windows only when the records of the whole launch
+ * do not fit) */
+static int
+batch_window_env(void)
+{
+    const char *e = getenv("LAMEHIP_MID_WINDOW");
+    long const v = e ? strtol(e, nullptr, 10) : 0;
+    return (v > 0 && v < (1l << 30)) ? (int) v : 0;
+}
+
+#define LH_MID_WINDOW_MIN 64    /* frames: below that the fused kernel is the better launch (a sub-launch ends with its slowest stream) */
+
+/* records a launch in windows of w frames needs at once (every stream's first window is its largest) */
+static long long
+batch_window_records(const lamehip_batch * b, const LhStreamDesc * h_descs, int w)
+{
+    long long n = 0;
+    for (int s = 0; s < b->B; s++) {
+        int const nf = h_descs[s].frame_end - h_descs[s].frame_begin;
+        if (nf > 0)
+            n += nf < w ? nf : w;
+    }
+    return n;
+}
+
+/* What the launch of the frames `h_descs' names will be: the split pipeline over the whole launch when its analysis records
+ * fit the device (34 KB per frame: 81 GB at 1024 x 60 s), else the split pipeline over windows of as many frames per stream as
+ * do fit -- each window a launch of its own, analysis kernels then encode kernel, the streams' state carried in
+ * LhStreamState as between two launches of an incremental batch --, else (under LH_MID_WINDOW_MIN frames per window, more
+ * than 65 535 streams, LAMEHIP_FUSED / LAMEHIP_SPLIT_DENY) the fused kernel.  The windows' descriptors go to HBM here, on the
+ * batch's stream.  Allocates: call it before the devices' launch order is taken. */
+static int
+batch_plan(lamehip_batch * b, const LhStreamDesc * h_descs, LhLaunchPlan * p)
+{
+    long long free_records = 0;
+    int     nactive = 0;
+    memset(p, 0, sizeof(*p));
+    for (int s = 0; s < b->B; s++) {
+        int const nf = h_descs[s].frame_end - h_descs[s].frame_begin;
+        if (nf > 0) {
+            p->total += nf;
+            nactive++;
+            if (nf > p->max_frames)
+                p->max_frames = nf;
+        }
+    }
+    p->nwin = 1;
+    /* (the analysis and sub-band kernels index the stream by blockIdx.y, which ends at 65535: a larger batch keeps the
+     * fused kernel, whose grid is one-dimensional) */
+    if (!(b->split && p->total > 0 && b->B <= 65535 && !batch_split_denied()))
+        return 0;
+    int     w = batch_window_env();
+    if (w >= p->max_frames)
+        w = 0;
+    if (w == 0) {
+        if (batch_mid_reserve(b, p->total, &free_records) == 0) {
+            p->split = 1;
+            return 0;
+        }
+        w = nactive ? (int) (free_records / nactive < p->max_frames ? free_records / nactive : p->max_frames) : 0;
+        if (w < LH_MID_WINDOW_MIN) {
+            size_t const n = strlen(g_err);
+            snprintf(g_err + n, sizeof(g_err) - n, ": fused kernel");
+            return 0;
+        }
+    }
+    if (batch_mid_reserve(b, batch_window_records(b, h_descs, w)) != 0)
+        return 0;
+    p->split = 1;
+    p->window = w;
+    p->nwin = (p->max_frames + w - 1) / w;
+    /* window k of a stream: its frames [begin + k w, begin + (k + 1) w) at the payload's places, their records from the
+     * start of the pool on, stream after stream; the flush goes with the stream's last frame (a stream without frames
+     * keeps its descriptor in window 0: what an incremental batch's launch may hold) */
+    b->h_wdesc.resize((size_t) p->nwin * (size_t) b->B);
+    for (int k = 0; k < p->nwin; k++) {
+        long long at = 0;
+        for (int s = 0; s < b->B; s++) {
+            LhStreamDesc d = h_descs[s];
+            int const nf = d.frame_end > d.frame_begin ? d.frame_end - d.frame_begin : 0;
+            long long const lo = (long long) k * w < nf ? (long long) k * w : nf, hi = lo + w < nf ? lo + w : nf;
+            if (nf > 0) {
+                d.out_index = h_descs[s].out_index + lo;
+                d.frame_begin = h_descs[s].frame_begin + (int) lo;
+                d.frame_end = h_descs[s].frame_begin + (int) hi;
+                d.flush = h_descs[s].flush && hi == nf && lo < hi;
+                d.mid_rel = (int) (at - d.out_index);
+                at += hi - lo;
+            }
+            else if (k > 0)
+                d.flush = 0;
+            b->h_wdesc[(size_t) k * (size_t) b->B + (size_t) s] = d;
+        }
+    }
+    HIPCHK(b->d_wdesc.reserve(b->h_wdesc.size()));
+    HIPCHK(hipMemcpyAsync(b->d_wdesc.get(), b->h_wdesc.data(), b->h_wdesc.size() * sizeof(LhStreamDesc), hipMemcpyHostToDevice, b->stream));
+    while (b->ev_win.size() < 3 * (size_t) p->nwin) {
+        LhEvent e;
+        if (e.create() != hipSuccess)
+            return set_err("hipEventCreate", hipGetLastError());
+        b->ev_win.push_back(std::move(e));
+    }
+    return 0;
+}
+
+/* one launch of the batch's frames [frame_begin, frame_end) per stream, as `descs' (device copy) / `h_descs' say, between
+ * ev0 and ev1 on the batch's stream, the way batch_plan decided */
+static int
+batch_launch(lamehip_batch * b, const int16_t * pcm, const float *pcmf, const LhStreamDesc * descs, const LhLaunchPlan & p, uint8_t * bytes)
+{
+    int     rc = 0, split = p.split;
+    void   *const stream = (void *) (hipStream_t) b->stream;
+    LhMidPools const mid = { b->mid.get() };
+    if (split && !p.window && !b->ev_part[0]) {
+        if (b->ev_part[0].create() != hipSuccess || b->ev_part[1].create() != hipSuccess)
+            return set_err("hipEventCreate", hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(b->ev0, b->stream));
+    if (split && p.window) {
+        for (int k = 0; k < p.nwin && !rc; k++) {
+            int const left = p.max_frames - k * p.window;
+            hipEvent_t between[2] = { b->ev_win[3 * (size_t) k + 1], b->ev_win[3 * (size_t) k + 2] };
+            HIPCHK(hipEventRecord(b->ev_win[3 * (size_t) k], b->stream));
+            rc = b->dc.launch_split(pcm, pcmf, b->d_wdesc.get() + (size_t) k * (size_t) b->B, b->d_state.get(), b->d_out.get(), bytes,
+                                    b->B, left < p.window ? left : p.window, mid, stream, between);
+        }
+    }
+    else if (split) {
+        hipEvent_t between[2] = { b->ev_part[0], b->ev_part[1] };
+        rc = b->dc.launch_split(pcm, pcmf, descs, b->d_state.get(), b->d_out.get(), bytes, b->B, p.max_frames, mid, stream, between);
+    }
+    else
+        rc = b->dc.launch(pcm, pcmf, descs, b->d_state.get(), b->d_out.get(), bytes, b->B, stream);
+    if (rc)
+        return set_err("kernel launch", (hipError_t) rc);
+    HIPCHK(hipEventRecord(b->ev1, b->stream));
+    if (b->ev_wait.create(hipEventDisableTiming) != hipSuccess)
+        (void) hipGetLastError();
+    if (b->ev_wait)
+        HIPCHK(hipEventRecord(b->ev_wait, b->stream));
+    b->last_split = split;
+    b->last_windows = (split && p.window) ? p.nwin : 1;
+    return 0;
+}
+
+static int
+batch_padding(const lamehip_batch * b, int s)
+{
+    return b->rate_in ? b->padding[(size_t) s] : lh_end_padding_fs(b->len[(size_t) s], fs_of(b->cfg));
+}
+
+/* every stream back to its initial state: a device-to-device copy of the pristine image on the batch's own
+ * stream (a host copy on the null stream would wait for every other batch's work in flight) */
+static int
+batch_reset_states(lamehip_batch * b)
+{
+    if (!b->d_state0.get()) {
+        std::vector < LhStreamState > s((size_t) b->B);
+        for (int i = 0; i < b->B; i++)
+            lh_state_init(&s[(size_t) i], &b->cfg);
+        HIPCHK(b->d_state0.alloc(s.size()));
+        HIPCHK(hipMemcpy(b->d_state0.get(), s.data(), s.size() * sizeof(LhStreamState), hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpyAsync(b->d_state.get(), b->d_state0.get(), (size_t) b->B * sizeof(LhStreamState), hipMemcpyDeviceToDevice, b->stream));
+    b->encoded = 0;
+    return 0;
+}
+
+extern "C" lamehip_batch *
+lamehip_batch_create(const lame_t proto, int nstreams, long capacity_samples)
+{
+    int     dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess)
+        dev = 0;
+    return lamehip_batch_create_on(dev, proto, nstreams, capacity_samples);
+}
+
+/* a batch on HIP device `device' (its pools, state, stream and launches live there whatever device
+ * is current in the calling thread); the handle only provides the settings and may belong to
+ * another device */
+extern "C" lamehip_batch *
+lamehip_batch_create_on(int device, const lame_t proto, int nstreams, long capacity_samples)
+{
+    lamehip_batch *b;
+    if (device < 0 || device >= lamehip_device_count()) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_create_on: no HIP device %d", device);
+        return nullptr;
+    }
+    LhDeviceScope const on_device(device);
+    if (!valid(proto) || !proto->inited || !proto->have_device || nstreams <= 0
+        || capacity_samples <= 0) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_create: need an initialised handle on a HIP device");
+        return nullptr;
+    }
+    b = new(std::nothrow) lamehip_batch();
+    if (!b)
+        return nullptr;
+    b->device = device;
+    b->cfg = proto->cfg;
+    b->tab = (LhTables *) malloc(sizeof(LhTables));
+    if (!b->tab) {
+        delete  b;
+        return nullptr;
+    }
+    memcpy(b->tab, proto->tab, sizeof(LhTables));
+    b->B = nstreams;
+    b->cap = capacity_samples;
+    b->len.assign((size_t) nstreams, 0);
+    b->nframes.assign((size_t) nstreams, 0);
+    b->out_off.assign((size_t) nstreams, 0);
+    b->h_desc.resize((size_t) nstreams);
+    b->bytes_off.assign((size_t) nstreams, 0);
+    b->padding.assign((size_t) nstreams, 0);
+    b->row_dirty.assign((size_t) nstreams, 0);
+    b->split = batch_use_split();
+    if (proto->rs) {
+        /* the s16 pool shrinks to nothing, the converted signal (plus the flush's tail) lives in a float pool */
+        b->rate_in = proto->p.samplerate;
+        b->rs = (LhResampler *) malloc(sizeof(LhResampler));
+        b->capf = (long) ((double) capacity_samples / proto->rs->ratio) + 4 * 1152 + 64;
+        capacity_samples = 1;
+        if (!b->rs || b->d_pcmf.alloc((size_t) nstreams * 2 * (size_t) b->capf) != hipSuccess) {
+            snprintf(g_err, sizeof(g_err), "lamehip_batch_create: device allocation failed");
+            lamehip_batch_destroy(b);
+            return nullptr;
+        }
+    }
+    if (b->dc.upload(b->cfg, *b->tab) != 0
+        || b->d_pcm.alloc((size_t) nstreams * 2 * (size_t) capacity_samples) != hipSuccess
+        || b->d_state.alloc((size_t) nstreams) != hipSuccess
+        || b->d_desc.alloc((size_t) nstreams) != hipSuccess
+        || b->stream.create() != hipSuccess
+        || b->ev0.create() != hipSuccess || b->ev1.create() != hipSuccess
+        || hipMemset(b->d_pcm.get(), 0, (size_t) nstreams * 2 * (size_t) capacity_samples * 2) != hipSuccess
+        || batch_reset_states(b) != 0) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_create: device allocation failed");
+        lamehip_batch_destroy(b);
+        return nullptr;
+    }
+    return b;
+}
+
+extern "C" void
+lamehip_batch_destroy(lamehip_batch * b)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b)
+        return;
+    for (size_t i = 0; i < b->packer.size(); i++)
+        lh_bs_free(&b->packer[i]);
+    lh_rs_trunk_free(&b->trunk);
+    free(b->rs);
+    free(b->tab);
+    b->dc.release();
+    delete  b;                  /* (what the owners hold goes here, on the batch's device) */
+}
+
+/* Device conversion: stream s will be n input samples long.  The host plans -- the trunk grows to the stream's full
+ * chunks, the stream's own last blocks are kept with it -- and with that knows the converted length, the frame count
+ * and the end padding; the samples are not looked at. */
+static int
+batch_plan_stream(lamehip_batch * b, int s, long n)
+{
+    int const fs = fs_of(b->cfg);
+    std::vector < LhRsBlock > &tail = b->tail[(size_t) s];
+    long    conv = 0;
+    int     frames = 0, padding = 0, ntail;
+    if (lh_rs_trunk_extend(b->rs, &b->trunk, n / fs) != 0) {
+        snprintf(g_err, sizeof(g_err), "out of memory (conversion plan)");
+        return -2;
+    }
+    tail.resize(16);
+    ntail = lh_rs_plan_tail(b->rs, &b->trunk, n, tail.data(), (int) tail.size(), &conv, &frames, &padding);
+    if (ntail > (int) tail.size()) {
+        tail.resize((size_t) ntail);
+        ntail = lh_rs_plan_tail(b->rs, &b->trunk, n, tail.data(), (int) tail.size(), &conv, &frames, &padding);
+    }
+    if (ntail < 0)
+        return -1;
+    tail.resize((size_t) ntail);
+    if (conv > b->capf) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_pcm: converted stream (%ld samples) exceeds the pool", conv);
+        return -1;
+    }
+    /* (the kernel stages a block's span of input in LDS: nothing the converter cuts is longer than LH_RS_SPAN_MAX, a
+     * block being at most 1152 input samples and the taps before them; checked all the same, before anything runs) */
+    for (const LhRsBlock & k:tail) {
+        if (k.made > 0 && lh_rs_locate(b->rs->ratio, b->rs->taps, b->rs->phases, k.start, k.made - 1).first + b->rs->taps + 1
+            - lh_rs_locate(b->rs->ratio, b->rs->taps, b->rs->phases, k.start, 0).first > LH_RS_SPAN_MAX) {
+            snprintf(g_err, sizeof(g_err), "conversion plan: a block spans more input than the device kernel stages");
+            return -1;
+        }
+    }
+    b->len_in[(size_t) s] = n;
+    b->len[(size_t) s] = conv;
+    b->nframes[(size_t) s] = frames;
+    b->padding[(size_t) s] = padding;
+    b->rs_dirty[(size_t) s] = 1;
+    return 0;
+}
+
+/* input samples of stream s in the s16 pool */
+static long
+batch_len_in(const lamehip_batch * b, int s)
+{
+    return b->dev_rs ? b->len_in[(size_t) s] : b->len[(size_t) s];
+}
+
+extern "C" int
+lamehip_batch_set_length(lamehip_batch * b, int s, long n)
+{
+    if (!b || s < 0 || s >= b->B || n < 0 || (n > b->cap && !b->dev_rs) || (b->rate_in && !b->dev_rs))
+        return -1;              /* (a batch that converts on the host needs the samples themselves: lamehip_batch_set_pcm) */
+    if (b->dev_rs && n > b->cap) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_length: stream of %ld samples exceeds the pool (%ld per stream)", n, b->cap);
+        return -1;
+    }
+    b->pcm_given = 1;
+    if (b->dev_rs)
+        return batch_plan_stream(b, s, n);
+    b->len[(size_t) s] = n;
+    b->nframes[(size_t) s] = lh_total_frames_fs(n, fs_of(b->cfg));
+    return 0;
+}
+
+/* A stream of a converting batch: what the reference makes of it when its frontend feeds
+ * lame_encode_buffer 1152 input samples at a time and then flushes (lame.c:1708-1772, 2075-2120;
+ * the same bookkeeping as the handle path above, without a device in the loop). */
+static int
+batch_convert_stream(lamehip_batch * b, int s, const short *l, const short *r, long n)
+{
+    float  *ol = nullptr, *orr = nullptr;
+    long    conv = 0;
+    int     frames = 0, padding = 0;
+    if (lh_rs_convert_stream(b->rs, b->rate_in, b->cfg.samplerate, fs_of(b->cfg), mfn_of(b->cfg), b->cfg.channels, b->cfg.pcm_scale,
+                             b->cfg.pcm_mix, b->cfg.pcm_scale_r, l, r, n, &ol, &orr, &conv, &frames, &padding) != 0) {
+        snprintf(g_err, sizeof(g_err), "out of memory (sample rate converter)");
+        return -2;
+    }
+    if (conv > b->capf) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_pcm: converted stream (%ld samples) exceeds the pool", conv);
+        lh_rs_free(ol);
+        lh_rs_free(orr);
+        return -1;
+    }
+    b->len[(size_t) s] = conv;
+    b->nframes[(size_t) s] = frames;
+    b->padding[(size_t) s] = padding;
+    hipError_t e = hipSuccess;
+    if (conv > 0) {
+        e = hipMemcpy(b->d_pcmf.get() + ((size_t) s * 2) * (size_t) b->capf, ol, (size_t) conv * sizeof(float), hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = hipMemcpy(b->d_pcmf.get() + ((size_t) s * 2 + 1) * (size_t) b->capf, orr, (size_t) conv * sizeof(float), hipMemcpyHostToDevice);
+    }
+    lh_rs_free(ol);
+    lh_rs_free(orr);
+    if (e != hipSuccess)
+        return set_err("hipMemcpy", e);
+    return 0;
+}
+
+extern "C" short *lamehip_batch_pcm_host_ptr(lamehip_batch * b);
+
+/* the mirror for lamehip_batch_set_pcm: made on first use unless the pool is larger than LAMEHIP_PINNED_MAX_MB
+ * (default 4096) of pinned host memory */
+static int16_t *
+batch_host_pool(lamehip_batch * b)
+{
+    if (!b->h_pcm.get() && (!b->rate_in || b->dev_rs)) {
+        const char *e = getenv("LAMEHIP_PINNED_MAX_MB");
+        double const limit = (e ? atof(e) : 4096.0) * 1048576.0;
+        if ((double) b->B * 4.0 * (double) b->cap > limit)
+            return nullptr;
+        (void) lamehip_batch_pcm_host_ptr(b);
+    }
+    return b->h_pcm.get();
+}
+
+/* the pinned mirror is about to be rewritten by the host: an upload out of it that is still on its way must have
+ * finished (the device-side wait in lamehip_batch_encode says nothing to the host) */
+static int
+batch_mirror_quiesce(lamehip_batch * b)
+{
+    if (b->up_inflight) {
+        HIPCHK(hipEventSynchronize(b->ev_up));
+        b->up_inflight = 0;
+    }
+    return 0;
+}
+
+extern "C" int
+lamehip_batch_set_pcm(lamehip_batch * b, int s, const short *l, const short *r, long n)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (b && b->rate_in && !b->dev_rs) {
+        if (s < 0 || s >= b->B || n < 0)
+            return -1;
+        b->pcm_given = 1;
+        if (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f)
+            r = l;
+        return batch_convert_stream(b, s, l, r, n);
+    }
+    if (lamehip_batch_set_length(b, s, n) != 0)
+        return -1;
+    if (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f)
+        r = l;                  /* mono: the second plane mirrors the first, the kernel never uses it */
+    if (batch_host_pool(b) != nullptr) {
+        if (batch_mirror_quiesce(b) != 0)
+            return LAMEHIP_ERR_DEVICE;
+        /* into the pinned mirror; the rows travel with the next lamehip_batch_upload / _encode, all streams'
+         * in one asynchronous copy (the reference's seam: lame_encode_buffer copies into mfbuf, lame.c:1672) */
+        memcpy(b->h_pcm.get() + ((size_t) s * 2) * (size_t) b->cap, l, (size_t) n * 2);
+        memcpy(b->h_pcm.get() + ((size_t) s * 2 + 1) * (size_t) b->cap, r, (size_t) n * 2);
+        if (!b->row_dirty[(size_t) s]) {
+            b->row_dirty[(size_t) s] = 1;
+            b->n_dirty++;
+        }
+        return 0;
+    }
+    /* the pool is too large to mirror in pinned memory: straight to HBM, stream by stream */
+    HIPCHK(hipMemcpy(b->d_pcm.get() + ((size_t) s * 2) * (size_t) b->cap, l, (size_t) n * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b->d_pcm.get() + ((size_t) s * 2 + 1) * (size_t) b->cap, r, (size_t) n * 2, hipMemcpyHostToDevice));
+    return 0;
+}
+
+/* The pinned mirror of the batch's s16 pool, [stream][2][capacity] like the pool itself: the caller may
+ * decode straight into it (then lamehip_batch_set_length + lamehip_batch_mark_pcm, or lamehip_batch_set_pcm,
+ * which copies into it).  NULL for a converting batch or when the mirror cannot be had. */
+extern "C" short *
+lamehip_batch_pcm_host_ptr(lamehip_batch * b)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b)
+        return nullptr;
+    if (!b->h_pcm.get() && (!b->rate_in || b->dev_rs) && b->h_pcm.alloc((size_t) b->B * 2 * (size_t) b->cap) != hipSuccess)
+        (void) hipGetLastError();
+    /* whoever asks for the pointer is about to write through it: no upload may still be reading the mirror.  (A caller
+     * that keeps the pointer across rounds asks again -- or calls lamehip_batch_set_pcm -- before it rewrites rows that
+     * an asynchronous lamehip_batch_upload / _encode has taken.) */
+    if (b->h_pcm.get() && batch_mirror_quiesce(b) != 0)
+        return nullptr;
+    if (b->h_pcm.get())
+        b->pcm_given = 1;
+    return b->h_pcm.get();
+}
+
+/* stream s's rows of the mirror were written by the caller: they travel with the next upload */
+extern "C" int
+lamehip_batch_mark_pcm(lamehip_batch * b, int s)
+{
+    if (!b || s < 0 || s >= b->B || !b->h_pcm.get())
+        return -1;
+    if (b->dev_rs)
+        b->rs_dirty[(size_t) s] = 1;    /* new samples: the stream is converted again */
+    if (!b->row_dirty[(size_t) s]) {
+        b->row_dirty[(size_t) s] = 1;
+        b->n_dirty++;
+    }
+    return 0;
+}
+
+/* Asynchronous H2D of everything that changed in the mirror, on the batch's stream (lamehip_batch_encode does
+ * this itself when something is pending).  One copy when every stream changed and the streams fill their rows,
+ * else one per row. */
+static int
+batch_copy_streams(lamehip_batch * b)
+{
+    if (!b->up_stream) {
+        HIPCHK(b->up_stream.create(hipStreamNonBlocking));
+        HIPCHK(b->down_stream.create(hipStreamNonBlocking));
+        HIPCHK(b->ev_up.create(hipEventDisableTiming));
+        HIPCHK(b->ev_sum.create(hipEventDisableTiming));
+        HIPCHK(b->ev_down.create(hipEventDisableTiming));
+    }
+    return 0;
+}
+
+extern "C" int
+lamehip_batch_upload(lamehip_batch * b)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b)
+        return -1;
+    if (b->n_dirty == 0 || !b->h_pcm.get())
+        return 0;
+    if (batch_copy_streams(b) != 0)
+        return LAMEHIP_ERR_DEVICE;
+    /* the pool may still be read by the kernel of the previous round (also after a reset, which clears `encoded') */
+    if (b->launched)
+        HIPCHK(hipStreamWaitEvent(b->up_stream, b->ev1, 0));
+    {
+        long long used = 0;
+        for (int s = 0; s < b->B; s++)
+            used += batch_len_in(b, s);
+        if (b->n_dirty == b->B && used * 10 >= (long long) b->B * b->cap * 9)
+            HIPCHK(hipMemcpyAsync(b->d_pcm.get(), b->h_pcm.get(), (size_t) b->B * 2 * (size_t) b->cap * 2, hipMemcpyHostToDevice, b->up_stream));
+        else
+            for (int s = 0; s < b->B; s++) {
+                size_t const n = (size_t) batch_len_in(b, s) * 2;
+                if (!b->row_dirty[(size_t) s] || n == 0)
+                    continue;
+                for (int ch = 0; ch < 2; ch++) {
+                    size_t const at = ((size_t) s * 2 + (size_t) ch) * (size_t) b->cap;
+                    HIPCHK(hipMemcpyAsync(b->d_pcm.get() + at, b->h_pcm.get() + at, n, hipMemcpyHostToDevice, b->up_stream));
+                }
+            }
+    }
+    HIPCHK(hipEventRecord(b->ev_up, b->up_stream));
+    b->up_pending = 1;
+    b->up_inflight = 1;
+    b->row_dirty.assign((size_t) b->B, 0);
+    b->n_dirty = 0;
+    return 0;
+}
+
+extern "C" int
+lamehip_batch_set_pcm_device(lamehip_batch * b, int s, const void *dl, const void *dr, long n)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (lamehip_batch_set_length(b, s, n) != 0)
+        return -1;
+    if (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f)
+        dr = dl;
+    if (b->up_pending || b->up_inflight) {      /* an upload of the mirror is on its way into the same pool */
+        HIPCHK(hipStreamSynchronize(b->up_stream));
+        b->up_inflight = 0;
+    }
+    if (b->row_dirty[(size_t) s]) {     /* what the mirror holds for this stream is superseded */
+        b->row_dirty[(size_t) s] = 0;
+        b->n_dirty--;
+    }
+    HIPCHK(hipMemcpy(b->d_pcm.get() + ((size_t) s * 2) * (size_t) b->cap, dl, (size_t) n * 2, hipMemcpyDeviceToDevice));
+    HIPCHK(hipMemcpy(b->d_pcm.get() + ((size_t) s * 2 + 1) * (size_t) b->cap, dr, (size_t) n * 2, hipMemcpyDeviceToDevice));
+    return 0;
+}
+
+extern "C" void *
+lamehip_batch_pcm_device_ptr(lamehip_batch * b)
+{
+    return (b && (!b->rate_in || b->dev_rs)) ? (void *) b->d_pcm.get() : nullptr;
+}
+
+
+/* ---- incremental use of a batch: lame_encode_buffer semantics for many streams at once -------
+ * (reference lame.c:1672-1775: every call appends samples to a stream and encodes the frames that
+ * became complete; the output lags the input by the priming).  lamehip_batch_append stages a chunk
+ * per stream in pinned host memory, lamehip_batch_encode_available moves all staged chunks to HBM
+ * with ONE asynchronous copy, encodes every stream's newly complete frames with ONE launch and packs
+ * them, lamehip_batch_drain hands a stream's new bytes over -- the bytes lame_encode_buffer would
+ * have returned for the same calls --, lamehip_batch_finish is lame_encode_flush for all streams. */
+static int
+batch_incremental_begin(lamehip_batch * b)
+{
+    if (b->incremental)
+        return 0;
+    if (b->rate_in || b->dev_pack) {
+        snprintf(g_err, sizeof(g_err), "incremental batches take the encoder's own input rate and the host packer");
+        return -1;
+    }
+    if (batch_reset_states(b) != 0)
+        return LAMEHIP_ERR_DEVICE;
+    b->fed.assign((size_t) b->B, 0);
+    b->done.assign((size_t) b->B, 0);
+    b->staged.assign((size_t) b->B, 0);
+    b->pending.assign((size_t) b->B, std::vector < unsigned char >());
+    b->last.resize((size_t) b->B);
+    b->have_last.assign((size_t) b->B, 0);
+    b->packer.resize((size_t) b->B);
+    for (int s = 0; s < b->B; s++)
+        if (lh_bs_init_sized(&b->packer[(size_t) s], 65536) != 0)
+            return -2;
+    b->incremental = 1;
+    return 0;
+}
+
+#define LH_STAGE_SEGS 4096       /* chunks per trip to HBM */
+#define LH_STAGE_SAMPLES (8L << 20)     /* the arena: 8 M samples = 16 MB; what is staged beyond goes to HBM at once */
+
+/* the staging area, made once: descriptors, chunk table, arena */
+static int
+batch_stage_reserve(lamehip_batch * b)
+{
+    long const arena_at = ((long) b->B * (long) sizeof(LhStreamDesc) + (long) LH_STAGE_SEGS * 16 + 63) & ~63L;
+    long const bytes = arena_at + LH_STAGE_SAMPLES * 2;
+    if (b->h_stage.get())
+        return 0;
+    if (b->h_stage.alloc((size_t) bytes) != hipSuccess || b->d_stage.alloc((size_t) bytes) != hipSuccess) {
+        b->h_stage.release();   /* (both or neither) */
+        return set_err("staging allocation", hipErrorOutOfMemory);
+    }
+    b->stage_arena_at = arena_at;
+    b->stage_cap = LH_STAGE_SAMPLES;
+    b->stage_used = 0;
+    b->stage_nseg = 0;
+    return 0;
+}
+
+/* what is staged goes to the pool: one copy of the chunk table and of the arena's bytes in use, one scatter
+ * launch; wait = the arena is free again on return (it is about to be refilled) */
+static int
+batch_stage_flush(lamehip_batch * b, int wait)
+{
+    size_t const segs_at = (size_t) b->B * sizeof(LhStreamDesc);
+    if (b->stage_nseg > 0) {
+        int     rc;
+        HIPCHK(hipMemcpyAsync(b->d_stage.get() + segs_at, b->h_stage.get() + segs_at, (size_t) b->stage_nseg * 16, hipMemcpyHostToDevice,
+                              b->stream));
+        HIPCHK(hipMemcpyAsync(b->d_stage.get() + b->stage_arena_at, b->h_stage.get() + b->stage_arena_at, (size_t) b->stage_used * 2,
+                              hipMemcpyHostToDevice, b->stream));
+        rc = lh_launch_scatter((const int16_t *) (b->d_stage.get() + b->stage_arena_at), b->d_pcm.get(), b->cap,
+                               (const int *) (b->d_stage.get() + segs_at), b->stage_nseg, (void *) (hipStream_t) b->stream);
+        if (rc)
+            return set_err("scatter launch", (hipError_t) rc);
+        for (int s = 0; s < b->B; s++) {
+            b->fed[(size_t) s] += b->staged[(size_t) s];
+            b->staged[(size_t) s] = 0;
+        }
+        b->stage_nseg = 0;
+        b->stage_used = 0;
+        if (wait)
+            HIPCHK(hipStreamSynchronize(b->stream));
+    }
+    return 0;
+}
+
+extern "C" int
+lamehip_batch_append(lamehip_batch * b, int s, const short *l, const short *r, int n)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int     rc;
+    if (!b || s < 0 || s >= b->B || n < 0 || (n > 0 && !l))
+        return -1;
+    if (b->finished) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_append: the batch is finished (lamehip_batch_reset starts it over)");
+        return -1;
+    }
+    if ((rc = batch_incremental_begin(b)) != 0)
+        return rc;
+    if (n == 0)
+        return 0;
+    if (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f)
+        r = l;
+    if (!r)
+        return -1;
+    if (b->fed[(size_t) s] + b->staged[(size_t) s] + n > b->cap) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_append: stream %d would exceed the batch's capacity of %ld samples", s, b->cap);
+        return -1;
+    }
+    if ((rc = batch_stage_reserve(b)) != 0)
+        return rc;
+    /* pieces of at most half the arena; when the arena or the chunk table is full, what is staged leaves for HBM */
+    while (n > 0) {
+        int const piece = ((long) n > b->stage_cap / 4) ? (int) (b->stage_cap / 4) : n;
+        int    *seg;
+        int16_t *arena = (int16_t *) (b->h_stage.get() + b->stage_arena_at);
+        if (b->stage_used + 2L * piece > b->stage_cap || b->stage_nseg == LH_STAGE_SEGS)
+            if ((rc = batch_stage_flush(b, 1)) != 0)
+                return rc;
+        seg = (int *) (b->h_stage.get() + (size_t) b->B * sizeof(LhStreamDesc)) + 4 * b->stage_nseg;
+        seg[0] = (int) b->stage_used;
+        seg[1] = s;
+        seg[2] = (int) (b->fed[(size_t) s] + b->staged[(size_t) s]);
+        seg[3] = piece;
+        memcpy(arena + b->stage_used, l, (size_t) piece * 2);
+        memcpy(arena + b->stage_used + piece, r, (size_t) piece * 2);
+        b->stage_used += 2L * piece;
+        b->stage_nseg++;
+        b->staged[(size_t) s] += piece;
+        l += piece;
+        r += piece;
+        n -= piece;
+    }
+    return 0;
+}
+
+/* frames of a stream that are complete once `fed' samples are in: frame f reads 1904 samples from
+ * 1152 f - 528 on (reference lame.c:1737-1766) */
+static int
+frames_complete(long fed, const LhConfig & c)
+{
+    long const have = fed + LH_MF_START;
+    return have >= mfn_of(c) ? (int) ((have - mfn_of(c)) / fs_of(c) + 1) : 0;
+}
+
+/* encode frames [done, upto[s]) of every stream and pack them into pending[]; `end' marks the
+ * streams' last frames (flush) */
+static int
+batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
+{
+    LhStreamDesc *descs = (LhStreamDesc *) b->h_stage.get();
+    long long total = 0;
+    int     rc;
+    for (int s = 0; s < b->B; s++) {
+        LhStreamDesc & d = descs[s];
+        int const nf = upto[(size_t) s] - b->done[(size_t) s];
+        memset(&d, 0, sizeof(d));
+        d.pcm_l = ((long long) s * 2) * b->cap;
+        d.pcm_r = ((long long) s * 2 + 1) * b->cap;
+        d.pcm_base = 0;
+        d.nsamples = b->fed[(size_t) s] + b->staged[(size_t) s];
+        d.out_index = total;
+        d.frame_begin = b->done[(size_t) s];
+        d.frame_end = upto[(size_t) s];
+        d.flush = end;
+        total += nf > 0 ? nf : 0;
+    }
+    HIPCHK(b->d_out.reserve((size_t) total, 1024));
+    /* descriptors, then what is staged (chunk table + the arena's bytes in use), then the scatter */
+    HIPCHK(hipMemcpyAsync(b->d_stage.get(), b->h_stage.get(), (size_t) b->B * sizeof(LhStreamDesc), hipMemcpyHostToDevice, b->stream));
+    if ((rc = batch_stage_flush(b, 0)) != 0)
+        return rc;
+    if (total == 0) {
+        HIPCHK(hipStreamSynchronize(b->stream));
+        return 0;
+    }
+    {
+        LhLaunchPlan plan;
+        if ((rc = batch_plan(b, descs, &plan)) != 0
+            || (rc = batch_launch(b, b->d_pcm.get(), (const float *) 0, (const LhStreamDesc *) b->d_stage.get(), plan, (uint8_t *) 0)) != 0)
+            return rc;
+    }
+    b->launched = 1;
+    b->h_new.resize((size_t) total);
+    HIPCHK(hipMemcpyAsync(b->h_new.data(), b->d_out.get(), (size_t) total * sizeof(LhFrameOut), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int s = 0; s < b->B; s++) {
+        LhBitstream *bs = &b->packer[(size_t) s];
+        std::vector < unsigned char >&out = b->pending[(size_t) s];
+        for (int f = b->done[(size_t) s]; f < upto[(size_t) s]; f++) {
+            const LhFrameOut & fo = b->h_new[(size_t) (descs[s].out_index + (f - descs[s].frame_begin))];
+            size_t  at;
+            int     k;
+            if (lh_bs_format_frame(bs, &b->cfg, b->tab, &fo) != 0) {
+                snprintf(g_err, sizeof(g_err), "inconsistent device payload (packer check %d) stream %d frame %d", bs->error, s, f);
+                return LAMEHIP_ERR_PAYLOAD;
+            }
+            at = out.size();
+            out.resize(at + (size_t) lh_bs_pending(bs));
+            k = lh_bs_copy(bs, out.data() + at, 0);
+            out.resize(at + (size_t) (k > 0 ? k : 0));
+            b->last[(size_t) s] = fo;
+            b->have_last[(size_t) s] = 1;
+        }
+        if (upto[(size_t) s] > b->done[(size_t) s])
+            b->done[(size_t) s] = upto[(size_t) s];
+    }
+    return (int) total;
+}
+
+extern "C" int
+lamehip_batch_encode_available(lamehip_batch * b)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    std::vector < int >upto;
+    int     rc;
+    if (!b)
+        return -1;
+    if (b->finished) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_encode_available: the batch is finished (lamehip_batch_reset starts it over)");
+        return -1;
+    }
+    if ((rc = batch_incremental_begin(b)) != 0)
+        return rc;
+    if ((rc = batch_stage_reserve(b)) != 0)
+        return rc;
+    upto.resize((size_t) b->B);
+    for (int s = 0; s < b->B; s++)
+        upto[(size_t) s] = frames_complete(b->fed[(size_t) s] + b->staged[(size_t) s], b->cfg);
+    return batch_encode_range(b, upto, 0);
+}
+
+/* lame_encode_flush for every stream of an incremental batch: the frames still owed for the samples
+ * fed (with the reference's end padding), then the stuffing that completes the last frame */
+extern "C" int
+lamehip_batch_finish(lamehip_batch * b)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    std::vector < int >upto;
+    int     rc, n;
+    if (!b)
+        return -1;
+    if (b->finished) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_finish: the batch is finished already (lamehip_batch_reset starts it over)");
+        return -1;
+    }
+    if ((rc = batch_incremental_begin(b)) != 0)
+        return rc;
+    if ((rc = batch_stage_reserve(b)) != 0)
+        return rc;
+    upto.resize((size_t) b->B);
+    for (int s = 0; s < b->B; s++) {
+        long const len = b->fed[(size_t) s] + b->staged[(size_t) s];
+        b->len[(size_t) s] = len;
+        b->nframes[(size_t) s] = lh_total_frames_fs(len, fs_of(b->cfg));
+        upto[(size_t) s] = b->nframes[(size_t) s];
+    }
+    n = batch_encode_range(b, upto, 1);
+    if (n < 0)
+        return n;
+    for (int s = 0; s < b->B; s++) {
+        LhBitstream *bs = &b->packer[(size_t) s];
+        std::vector < unsigned char >&out = b->pending[(size_t) s];
+        size_t  at = out.size();
+        int     k;
+        lh_bs_flush(bs, &b->cfg, b->have_last[(size_t) s] ? &b->last[(size_t) s] : nullptr);
+        out.resize(at + (size_t) lh_bs_pending(bs));
+        k = lh_bs_copy(bs, out.data() + at, 0);
+        out.resize(at + (size_t) (k > 0 ? k : 0));
+    }
+    b->finished = 1;
+    return n;
+}
+
+/* bytes of stream s produced since the last drain; -1 (and nothing taken) when they do not fit */
+extern "C" int
+lamehip_batch_drain(lamehip_batch * b, int s, unsigned char *out, int cap)
+{
+    int     n;
+    if (!b || !b->incremental || s < 0 || s >= b->B)
+        return -1;
+    n = (int) b->pending[(size_t) s].size();
+    if (n == 0)
+        return 0;
+    if (!out || cap < n)
+        return -1;
+    memcpy(out, b->pending[(size_t) s].data(), (size_t) n);
+    b->pending[(size_t) s].clear();
+    return n;
+}
+
+extern "C" int
+lamehip_batch_frames(lamehip_batch * b, int s)
+{
+    if (!b || s < 0 || s >= b->B)
+        return -1;
+    return b->nframes[(size_t) s];
+}
+
+extern "C" int
+lamehip_batch_reset(lamehip_batch * b)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b)
+        return -1;
+    if (b->incremental) {
+        /* an incremental batch starts over: nothing fed, nothing staged, fresh packers, nothing left to drain */
+        for (int s = 0; s < b->B; s++) {
+            lh_bs_free(&b->packer[(size_t) s]);
+            if (lh_bs_init_sized(&b->packer[(size_t) s], 65536) != 0)
+                return -2;
+            b->pending[(size_t) s].clear();
+        }
+        b->fed.assign((size_t) b->B, 0);
+        b->done.assign((size_t) b->B, 0);
+        b->staged.assign((size_t) b->B, 0);
+        b->have_last.assign((size_t) b->B, 0);
+        b->stage_used = 0;
+        b->stage_nseg = 0;
+        b->finished = 0;
+    }
+    return batch_reset_states(b);
+}
+
+/* The streams declared since their last conversion go through the device converter, on the batch's stream: the plan
+ * travels first (the trunk only as far as it has grown since the last time), then one launch. */
+static int
+batch_convert_launch(lamehip_batch * b)
+{
+    int     max_blocks = 0;
+    b->rs_ran = 0;
+    b->h_tails.clear();
+    b->h_rs_streams.clear();
+    for (int s = 0; s < b->B; s++) {
+        if (!b->rs_dirty[(size_t) s])
+            continue;
+        LhRsStream d;
+        d.n = b->len_in[(size_t) s];
+        d.stream = s;
+        d.ntrunk = b->trunk.after[d.n / b->trunk.fs].nblk;
+        d.tail_at = (int) b->h_tails.size();
+        d.ntail = (int) b->tail[(size_t) s].size();
+        b->h_tails.insert(b->h_tails.end(), b->tail[(size_t) s].begin(), b->tail[(size_t) s].end());
+        b->h_rs_streams.push_back(d);
+        if (d.ntrunk + d.ntail > max_blocks)
+            max_blocks = d.ntrunk + d.ntail;
+    }
+    if (b->h_rs_streams.empty())
+        return 0;
+    long const ntrunk = b->trunk.after[b->trunk.nchunks].nblk;
+    /* (twice what is needed; drained first: a conversion of the previous round may still be reading the old buffer) */
+    bool    fresh = false;
+    HIPCHK(b->d_rs_trunk.reserve((size_t) ntrunk, (size_t) ntrunk, b->stream, &fresh));
+    if (fresh)
+        b->rs_trunk_up = 0;
+    if (ntrunk > b->rs_trunk_up) {
+        HIPCHK(hipMemcpyAsync(b->d_rs_trunk.get() + b->rs_trunk_up, b->trunk.blk + b->rs_trunk_up,
+                              (size_t) (ntrunk - b->rs_trunk_up) * sizeof(LhRsBlock), hipMemcpyHostToDevice, b->stream));
+        b->rs_trunk_up = ntrunk;
+    }
+    HIPCHK(b->d_rs_tails.reserve(b->h_tails.size(), b->h_tails.size() + 64, b->stream));
+    if (!b->h_tails.empty())
+        HIPCHK(hipMemcpyAsync(b->d_rs_tails.get(), b->h_tails.data(), b->h_tails.size() * sizeof(LhRsBlock), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemcpyAsync(b->d_rs_streams.get(), b->h_rs_streams.data(), b->h_rs_streams.size() * sizeof(LhRsStream), hipMemcpyHostToDevice,
+                          b->stream));
+    LhRsParams p;
+    memset(&p, 0, sizeof(p));
+    p.ratio = b->rs->ratio;
+    p.m = lh_rs_matrix(b->cfg.pcm_scale, b->cfg.pcm_mix, b->cfg.pcm_scale_r);
+    p.taps = b->rs->taps;
+    p.phases = b->rs->phases;
+    p.channels = b->cfg.channels;
+    p.one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
+    p.cap_in = b->cap;
+    p.cap_out = b->capf;
+    HIPCHK(hipEventRecord(b->ev_rs[0], b->stream));
+    int const rc = lh_launch_resample(&p, b->d_rs_bank.get(), b->d_rs_trunk.get(), b->d_rs_tails.get(), b->d_rs_streams.get(), (int) b->h_rs_streams.size(),
+                                      max_blocks, b->d_pcm.get(), b->d_pcmf.get(), (void *) (hipStream_t) b->stream);
+    if (rc)
+        return set_err("conversion launch", (hipError_t) rc);
+    HIPCHK(hipEventRecord(b->ev_rs[1], b->stream));
+    b->rs_ran = 1;
+    b->rs_dirty.assign((size_t) b->B, 0);
+    return 0;
+}
+
+/* The byte pool's slice of stream s (device packing; else 0): room for every frame at the largest frame size the settings
+ * allow, +1 for CBR padding.  lamehip_batch_encode lays the streams out with it, lamehip_batch_reserve sizes the pool by it. */
+static long long
+batch_stream_bytes(const lamehip_batch * b, int s)
+{
+    int const top = (b->cfg.vbr == 0) ? b->cfg.bitrate_index : b->cfg.vbr_max_bitrate_index;
+    /* (the row of the stream's MPEG version: an MPEG-2 / 2.5 index stands for half the MPEG-1 rate or less) */
+    int const max_frame_bytes = (b->cfg.version + 1) * 72000 * lh_tag_kbps(b->cfg.version, top & 15) / b->cfg.samplerate + 1;
+    return b->dev_pack ? (long long) b->nframes[(size_t) s] * max_frame_bytes : 0;
+}
+
+/* room for a launch of `total' frames whose streams' slices add up to `bytes_total' */
+static int
+batch_pools_reserve(lamehip_batch * b, long long total, long long bytes_total)
+{
+    if (b->dev_pack)
+        HIPCHK(b->d_bytes.reserve((size_t) bytes_total));
+    HIPCHK(b->d_out.reserve((size_t) total));
+    return 0;
+}
+
+extern "C" int
+lamehip_batch_encode(lamehip_batch * b)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    long long total = 0, bytes_total = 0;
+    if (!b)
+        return -1;
+    if (b->incremental) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_encode: this batch is fed with lamehip_batch_append (incremental use)");
+        return -1;
+    }
+    /* a batch that has been encoded starts over: every call encodes the streams from their first
+     * sample, so the carried state must be the initial one */
+    if (b->encoded && batch_reset_states(b) != 0)
+        return LAMEHIP_ERR_DEVICE;
+    for (int s = 0; s < b->B; s++) {
+        LhStreamDesc & d = b->h_desc[(size_t) s];
+        b->out_off[(size_t) s] = total;
+        d.pcm_l = ((long long) s * 2) * (b->rate_in ? b->capf : b->cap);
+        d.pcm_r = ((long long) s * 2 + 1) * (b->rate_in ? b->capf : b->cap);
+        d.pcm_base = 0;
+        d.nsamples = b->len[(size_t) s];
+        d.out_index = total;
+        d.frame_begin = 0;
+        d.frame_end = b->nframes[(size_t) s];
+        d.flush = 1;
+        d.mid_rel = 0;
+        d.bytes_base = bytes_total;
+        d.bytes_cap = batch_stream_bytes(b, s);
+        b->bytes_off[(size_t) s] = bytes_total;
+        bytes_total += d.bytes_cap;
+        total += b->nframes[(size_t) s];
+    }
+    {
+        int const rc = batch_pools_reserve(b, total, bytes_total);
+        if (rc)
+            return rc;
+    }
+    if (b->n_dirty && lamehip_batch_upload(b) != 0)
+        return LAMEHIP_ERR_DEVICE;
+    if (b->up_pending) {
+        HIPCHK(hipStreamWaitEvent(b->stream, b->ev_up, 0));
+        b->up_pending = 0;
+    }
+    if (b->down_pending) {      /* the previous round's bytes must have left d_bytes */
+        HIPCHK(hipStreamWaitEvent(b->stream, b->ev_down, 0));
+        b->down_pending = 0;
+    }
+    HIPCHK(hipMemcpyAsync(b->d_desc.get(), b->h_desc.data(), (size_t) b->B * sizeof(LhStreamDesc),
+                          hipMemcpyHostToDevice, b->stream));
+    /* device conversion: behind the upload wait, in front of the analysis kernels */
+    if (b->dev_rs) {
+        int const rc = batch_convert_launch(b);
+        if (rc)
+            return rc;
+    }
+    /* (what the launch will be -- and the pool it needs -- before the device's launch order is taken: an allocation of tens
+     * of GB must not keep other batches' launches waiting) */
+    LhLaunchPlan plan;
+    {
+        int const rc = batch_plan(b, b->h_desc.data(), &plan);
+        if (rc)
+            return rc;
+    }
+    {
+        /* Launches that fill the device run one after the other, in launch order, whatever HIP streams their batches
+         * own: a launch of >= 512 streams keeps every SIMD's register file and every CU's LDS (2 x 256 VGPRs, 4 x 40 KB),
+         * so a second one has nothing to gain from being dispatched early -- and measured on the MI355X it loses: dispatched
+         * while the first still runs, its workgroups end up resident in two rounds (kernel 176 ms alone, 329 ms behind
+         * another launch, every stream's own cycle count unchanged; tools/e2e_diag2.py), which cost the two-batch pipeline a
+         * third of its rate.  Copies on the batches' copy streams overlap the kernels as before. */
+        LhLaunchSerial & ser = launch_serial(b->device);
+        std::lock_guard < std::mutex > hold(ser.lock);
+        int const big = (b->B >= 512);
+        if (big && ser.ev)
+            HIPCHK(hipStreamWaitEvent(b->stream, ser.ev, 0));
+        int     rc = batch_launch(b, b->rate_in ? (const int16_t *) 0 : b->d_pcm.get(), b->rate_in ? b->d_pcmf.get() : (const float *) 0,
+                                  b->d_desc.get(), plan, b->dev_pack ? b->d_bytes.get() : (uint8_t *) 0);
+        if (rc)
+            return rc;
+        if (b->dev_pack) {
+            /* the two words per stream lamehip_batch_fetch copies first: gathered here, inside the serial order -- as a
+             * launch of its own behind the NEXT batch's kernel it found no free register file until that kernel was over
+             * (all of a launch's streams end within a frame or two of each other), and its batch came home one kernel late */
+            if (batch_copy_streams(b) != 0)
+                return LAMEHIP_ERR_DEVICE;
+            HIPCHK(b->d_sum.reserve((size_t) b->B * 2));
+            rc = lh_launch_summary(b->d_state.get(), b->d_sum.get(), b->B, (void *) (hipStream_t) b->stream);
+            if (rc)
+                return set_err("summary launch", (hipError_t) rc);
+            HIPCHK(hipEventRecord(b->ev_sum, b->stream));
+        }
+        if (big) {
+            if (!ser.ev)
+                HIPCHK(hipEventCreateWithFlags(&ser.ev, hipEventDisableTiming));
+            HIPCHK(hipEventRecord(ser.ev, b->stream));
+        }
+    }
+    b->launched = 1;
+    b->encoded = 1;
+    b->fetched = 0;
+    return 0;
+}
+
+/* Device-packed batches: start the way back -- per stream (bytes, status), then the bytes themselves, into
+ * pinned host memory, asynchronously on the batch's stream (behind the kernel).  lamehip_batch_bytes_ptr /
+ * lamehip_batch_get_bytes_all wait for it.  Calling it right after lamehip_batch_encode lets the copies of this
+ * batch run under the next batch's kernel. */
+extern "C" int
+lamehip_batch_fetch(lamehip_batch * b)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    long long total = 0;
+    if (!b || !b->encoded || !b->dev_pack)
+        return -1;
+    if (b->fetched)
+        return 0;
+    for (int s = 0; s < b->B; s++)
+        total += b->h_desc[(size_t) s].bytes_cap;
+    HIPCHK(b->d_sum.reserve((size_t) b->B * 2));
+    HIPCHK(b->h_sum.reserve((size_t) b->B * 2));
+    HIPCHK(b->h_bytes.reserve((size_t) total));
+    if (batch_copy_streams(b) != 0)
+        return LAMEHIP_ERR_DEVICE;
+    /* (the summary words were gathered right behind the kernel: lamehip_batch_encode) */
+    HIPCHK(hipStreamWaitEvent(b->down_stream, b->ev_sum, 0));
+    HIPCHK(hipMemcpyAsync(b->h_sum.get(), b->d_sum.get(), (size_t) b->B * 2 * sizeof(long long), hipMemcpyDeviceToHost, b->down_stream));
+    if (total > 0)
+        HIPCHK(hipMemcpyAsync(b->h_bytes.get(), b->d_bytes.get(), (size_t) total, hipMemcpyDeviceToHost, b->down_stream));
+    HIPCHK(hipEventRecord(b->ev_down, b->down_stream));
+    b->down_pending = 1;
+    b->fetched = 1;
+    return 0;
+}
+
+/* stream s's finished bytes in the batch's pinned buffer (valid until the batch is encoded again): returns
+ * their number, or a negative code */
+extern "C" long
+lamehip_batch_bytes_ptr(lamehip_batch * b, int s, const unsigned char **p)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    long    n;
+    if (!b || s < 0 || s >= b->B || !b->encoded || !b->dev_pack || !p)
+        return -1;
+    if (!b->fetched && lamehip_batch_fetch(b) != 0)
+        return LAMEHIP_ERR_DEVICE;
+    HIPCHK(hipStreamSynchronize(b->down_stream));
+    if (b->h_sum.get()[2 * s + 1] != 0) {
+        snprintf(g_err, sizeof(g_err), "device bit packer reported status %d for stream %d", (int) b->h_sum.get()[2 * s + 1], s);
+        return LAMEHIP_ERR_PAYLOAD;
+    }
+    n = (b->nframes[(size_t) s] == 0) ? 0 : (long) b->h_sum.get()[2 * s];
+    *p = b->h_bytes.get() + b->bytes_off[(size_t) s];
+    return n;
+}
+
+/* Device bit packing: the kernel also assembles each stream's finished MP3 bytes in HBM
+ * (lh_dev_emit.h); lamehip_batch_get_bytes then copies them out, no host packer involved.
+ * Set before lamehip_batch_encode. */
+extern "C" int
+lamehip_batch_set_device_packing(lamehip_batch * b, int on)
+{
+    if (!b)
+        return -1;
+    b->dev_pack = on != 0;
+    return 0;
+}
+
+/* Device rate conversion (a batch whose input rate differs from the encoder's): the input stays s16, in a pool at the
+ * input rate that takes PCM the way a batch without conversion does -- pinned mirror, device-resident input --, and
+ * lamehip_batch_encode converts it into the float pool with a kernel (lh_resample_dev.hip) in front of the analysis
+ * kernels.  Only before any PCM is handed over; off (the default): lamehip_batch_set_pcm converts on the host. */
+extern "C" int
+lamehip_batch_set_device_resampling(lamehip_batch * b, int on)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b)
+        return -1;
+    if (!b->rate_in) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_device_resampling: this batch does not convert (input rate = output rate)");
+        return -1;
+    }
+    if (b->pcm_given || b->encoded || b->incremental) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_device_resampling: only before any PCM is handed over");
+        return -1;
+    }
+    if (!on || b->dev_rs) {
+        b->dev_rs = on != 0 && b->dev_rs;
+        return 0;
+    }
+    /* everything new first: a failure leaves the batch as it was */
+    lh_rs_init(b->rs, b->rate_in, b->cfg.samplerate);
+    int const rows = 2 * b->rs->phases + 1;
+    size_t const pool = (size_t) b->B * 2 * (size_t) b->cap * sizeof(int16_t);
+    LhDevBuf < int16_t > pcm;
+    LhDevBuf < float >bank;
+    LhDevBuf < LhRsStream > streams;
+    LhEvent ev[2];
+    std::vector < float >h_bank((size_t) rows * LH_RS_ROW, 0.0f);
+    for (int k = 0; k < rows; k++)
+        memcpy(&h_bank[(size_t) k * LH_RS_ROW], b->rs->bank[k], (size_t) (b->rs->taps + 1) * sizeof(float));
+    hipError_t e = pcm.alloc(pool / sizeof(int16_t));
+    if (e == hipSuccess)
+        e = bank.alloc(h_bank.size());
+    if (e == hipSuccess)
+        e = streams.alloc((size_t) b->B);
+    if (e == hipSuccess)
+        e = ev[0].create();
+    if (e == hipSuccess)
+        e = ev[1].create();
+    if (e == hipSuccess)
+        e = hipMemset(pcm.get(), 0, pool);
+    if (e == hipSuccess)
+        e = hipMemcpy(bank.get(), h_bank.data(), h_bank.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        return set_err("lamehip_batch_set_device_resampling: device allocation", e);
+    }
+    b->d_pcm = std::move(pcm);  /* (in place of the one-sample placeholder of a batch that converts on the host) */
+    b->d_rs_bank = std::move(bank);
+    b->d_rs_streams = std::move(streams);
+    b->ev_rs[0] = std::move(ev[0]);
+    b->ev_rs[1] = std::move(ev[1]);
+    lh_rs_trunk_init(&b->trunk, fs_of(b->cfg), mfn_of(b->cfg));
+    b->len_in.assign((size_t) b->B, 0);
+    b->tail.assign((size_t) b->B, std::vector < LhRsBlock > ());
+    b->rs_dirty.assign((size_t) b->B, 0);
+    b->dev_rs = 1;
+    return 0;
+}
+
+/* test accessor: the converted signal of stream s as the encoder reads it (after lamehip_batch_set_pcm when the host
+ * converts, after lamehip_batch_encode when the device does); returns its length, or a negative code */
+extern "C" long
+lamehip_batch_get_converted(lamehip_batch * b, int s, float *l, float *r, long cap)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b || s < 0 || s >= b->B || !b->rate_in || !l || !r)
+        return -1;
+    if (b->dev_rs && b->rs_dirty[(size_t) s]) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_get_converted: stream %d has not been converted yet (lamehip_batch_encode)", s);
+        return -1;
+    }
+    long const n = b->len[(size_t) s];
+    if (n > cap)
+        return -1;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (n > 0) {
+        HIPCHK(hipMemcpy(l, b->d_pcmf.get() + ((size_t) s * 2) * (size_t) b->capf, (size_t) n * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(r, b->d_pcmf.get() + ((size_t) s * 2 + 1) * (size_t) b->capf, (size_t) n * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return n;
+}
+
+/* HIP-event time of the device conversion of the last lamehip_batch_encode (after lamehip_batch_sync); 0 when none ran */
+extern "C" float
+lamehip_batch_last_resample_ms(lamehip_batch * b)
+{
+    return b ? b->rs_ms : 0.0f;
+}
+
+/* bytes of one stream as the device packed them (audio frames incl. the final padding, no tag) */
+extern "C" long
+lamehip_batch_get_bytes(lamehip_batch * b, int s, unsigned char *out, long out_size)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    LhStreamState st;
+    long    n;
+    if (!b || s < 0 || s >= b->B || !b->encoded || !b->dev_pack)
+        return -1;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    HIPCHK(hipMemcpy(&st, b->d_state.get() + s, sizeof(st), hipMemcpyDeviceToHost));
+    if (st.status != 0) {
+        snprintf(g_err, sizeof(g_err), "device bit packer reported status %d for stream %d", st.status, s);
+        return LAMEHIP_ERR_PAYLOAD;
+    }
+    n = (long) st.em_next_header;
+    if (b->nframes[(size_t) s] == 0)
+        n = 0;
+    if (n > out_size)
+        return -1;
+    if (n > 0)
+        HIPCHK(hipMemcpy(out, b->d_bytes.get() + b->bytes_off[(size_t) s], (size_t) n, hipMemcpyDeviceToHost));
+    return n;
+}
+
+/* device-packed stream as a complete file image: the final Xing/Info + LAME tag frame, then the audio
+ * frames.  The tag's bookkeeping (frame count, bitrate table of contents, music CRC, mode extension of
+ * the last frame) is read back from the frame headers of the bytes themselves. */
+extern "C" long
+lamehip_batch_get_bytes_tagged(lamehip_batch * b, int s, unsigned char *out, long out_size)
+{
+    LhVbrTag v;
+    int     total, last_mode_ext = 0;
+    long    k, pos = 0;
+    if (!b || s < 0 || s >= b->B || !b->encoded || !b->dev_pack)
+        return -1;
+    total = lh_tag_init(&v, &b->cfg);
+    if (b->rate_in)
+        v.samplerate_in = b->rate_in;
+    if (out_size < total)
+        return -1;
+    k = lamehip_batch_get_bytes(b, s, out + total, out_size - total);
+    if (k < 0 || total == 0)
+        return k;
+    while (pos + 4 <= k) {
+        const unsigned char *h = out + total + pos;
+        int const bi = h[2] >> 4, pad = (h[2] >> 1) & 1;
+        int const kbps = lh_tag_kbps(b->cfg.version, bi);
+        int const size = (b->cfg.version + 1) * 72000 * kbps / b->cfg.samplerate + pad;
+        if (h[0] != 0xff || (h[1] & 0xe0) != 0xe0 || kbps <= 0 || size <= 0) {
+            snprintf(g_err, sizeof(g_err), "device-packed stream %d: lost frame sync at byte %ld", s, pos);
+            return LAMEHIP_ERR_PAYLOAD;
+        }
+        lh_tag_add_frame(&v, kbps);
+        last_mode_ext = (h[3] >> 4) & 3;
+        pos += size;
+    }
+    lh_tag_crc(&v, out + total, k);
+    if (lh_tag_frame(&v, &b->cfg, b->cfg.vbr_q, batch_padding(b, s), last_mode_ext, out, total) != total)
+        memset(out, 0, (size_t) total);         /* no frames: the reference leaves the placeholder */
+    return k + total;
+}
+
+/* all streams: stream s at out + s * out_stride, sizes[s] = bytes or a negative code */
+extern "C" int
+lamehip_batch_get_bytes_all(lamehip_batch * b, unsigned char *out, long out_stride, long *sizes)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int     bad = 0;
+    if (!b || !b->encoded || !b->dev_pack || !out || !sizes)
+        return -1;
+    if (lamehip_batch_fetch(b) != 0)
+        return LAMEHIP_ERR_DEVICE;
+    HIPCHK(hipStreamSynchronize(b->down_stream));
+    for (int s = 0; s < b->B; s++) {
+        long    n = (b->nframes[(size_t) s] == 0) ? 0 : (long) b->h_sum.get()[2 * s];
+        if (b->h_sum.get()[2 * s + 1] != 0)
+            n = LAMEHIP_ERR_PAYLOAD;
+        else if (n > out_stride)
+            n = -1;
+        sizes[s] = n;
+        if (n < 0)
+            bad++;
+        else if (n > 0)
+            memcpy(out + (size_t) s * (size_t) out_stride, b->h_bytes.get() + b->bytes_off[(size_t) s], (size_t) n);
+    }
+    return bad ? -1 : 0;
+}
+
+/* The buffers a launch of the batch's present streams needs -- payload, the analysis kernels' pool (split pipeline), the byte
+ * pool of the device packer -- allocated now instead of by the first lamehip_batch_encode (81 GB of pool at 1024 x 60 s: a
+ * caller that times its first launch calls this first). */
+extern "C" int
+lamehip_batch_reserve(lamehip_batch * b)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    long long total = 0, bytes_total = 0;
+    if (!b)
+        return -1;
+    if (b->incremental)
+        return 0;               /* (incremental batches launch what has arrived: sized per launch) */
+    for (int s = 0; s < b->B; s++) {
+        total += b->nframes[(size_t) s];
+        bytes_total += batch_stream_bytes(b, s);
+    }
+    {
+        int const rc = batch_pools_reserve(b, total, bytes_total);
+        if (rc)
+            return rc;
+    }
+    if (b->split && total > 0 && !batch_window_env())
+        (void) batch_mid_reserve(b, total);     /* (no room: the launch will run in windows, or take the fused kernel) */
+    return 0;
+}
+
+extern "C" int
+lamehip_batch_sync(lamehip_batch * b)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b)
+        return -1;
+    if (b->ev_wait && b->launched) {
+        /* The wait for the launch: the runtime's own waits spin on the stream's signal whatever the event's flags say
+         * (measured: one CPU per rank for the whole launch), so the event is polled between short sleeps -- at most 100 us
+         * late on a launch of tens to hundreds of milliseconds, and the CPU is free meanwhile. */
+        hipError_t q;
+        struct timespec nap = { 0, 100000 };
+        while ((q = hipEventQuery(b->ev_wait)) == hipErrorNotReady)
+            nanosleep(&nap, nullptr);
+        if (q != hipSuccess)
+            return set_err("hipEventQuery", q);
+    }
+    if (b->up_stream) {
+        HIPCHK(hipStreamSynchronize(b->up_stream));
+        HIPCHK(hipStreamSynchronize(b->down_stream));
+    }
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (b->encoded) {
+        float   ms = 0;
+        b->rs_ms = 0;
+        if (b->rs_ran && hipEventElapsedTime(&b->rs_ms, b->ev_rs[0], b->ev_rs[1]) != hipSuccess) {
+            (void) hipGetLastError();
+            b->rs_ms = 0;
+        }
+        if (hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess)
+            b->last_ms = ms;
+        b->part_ms[0] = b->part_ms[1] = b->part_ms[2] = 0;
+        if (b->last_split && b->last_windows > 1) {
+            /* a launch in windows: the three parts summed over the windows (a window ends where the next one starts) */
+            for (int k = 0; k < b->last_windows; k++) {
+                hipEvent_t const e0 = b->ev_win[3 * (size_t) k], e1 = b->ev_win[3 * (size_t) k + 1], e2 = b->ev_win[3 * (size_t) k + 2];
+                hipEvent_t const e3 = (k + 1 < b->last_windows) ? (hipEvent_t) b->ev_win[3 * (size_t) k + 3] : (hipEvent_t) b->ev1;
+                float   a = 0, s_ = 0, q = 0;
+                if (hipEventElapsedTime(&a, e0, e1) != hipSuccess || hipEventElapsedTime(&s_, e1, e2) != hipSuccess
+                    || hipEventElapsedTime(&q, e2, e3) != hipSuccess) {
+                    (void) hipGetLastError();
+                    b->part_ms[0] = b->part_ms[1] = b->part_ms[2] = 0.0f;
+                    break;
+                }
+                b->part_ms[0] += a;
+                b->part_ms[1] += s_;
+                b->part_ms[2] += q;
+            }
+        }
+        else if (b->last_split) {
+            if (hipEventElapsedTime(&b->part_ms[0], b->ev0, b->ev_part[0]) != hipSuccess
+                || hipEventElapsedTime(&b->part_ms[1], b->ev_part[0], b->ev_part[1]) != hipSuccess
+                || hipEventElapsedTime(&b->part_ms[2], b->ev_part[1], b->ev1) != hipSuccess) {
+                (void) hipGetLastError();
+                b->part_ms[0] = b->part_ms[1] = b->part_ms[2] = 0.0f;   /* (never a stale figure of an earlier launch) */
+            }
+        }
+    }
+    return 0;
+}
+
+extern "C" float
+lamehip_batch_last_kernel_ms(lamehip_batch * b)
+{
+    return b ? b->last_ms : 0.0f;
+}
+
+/* the last launch kernel by kernel (split pipeline): analysis kernels, sub-band kernel, encode kernel, in ms; returns 1 when
+ * the launch went through the split pipeline, 0 for the fused kernel (all of lamehip_batch_last_kernel_ms is that one kernel) */
+extern "C" int
+lamehip_batch_last_kernel_parts_ms(lamehip_batch * b, float *parts3)
+{
+    if (!b || !parts3)
+        return -1;
+    parts3[0] = b->part_ms[0];
+    parts3[1] = b->part_ms[1];
+    parts3[2] = b->part_ms[2];
+    return b->last_split;
+}
+
+/* sub-launches of the last launch: 1, or the number of frame windows the split pipeline worked through (batch_plan) */
+extern "C" int
+lamehip_batch_last_windows(lamehip_batch * b)
+{
+    return b ? b->last_windows : 0;
+}
+
+extern "C" int
+lamehip_batch_kernel_waves(lamehip_batch * b)
+{
+    return b ? 2 : 0;
+}
+
+extern "C" int
+lamehip_batch_get_frames(lamehip_batch * b, int s, void *frames_out, int max_frames)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int     n;
+    if (!b || s < 0 || s >= b->B || !b->encoded)
+        return -1;
+    n = b->nframes[(size_t) s];
+    if (n > max_frames)
+        n = max_frames;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    HIPCHK(hipMemcpy(frames_out, b->d_out.get() + b->out_off[(size_t) s], (size_t) n * sizeof(LhFrameOut),
+                     hipMemcpyDeviceToHost));
+    return n;
+}
+
+
+/* debug / profiling aid: raw LhStreamState of one stream */
+extern "C" int
+lamehip_batch_get_state(lamehip_batch * b, int s, void *out, int size)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b || s < 0 || s >= b->B || size < (int) sizeof(LhStreamState))
+        return -1;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    HIPCHK(hipMemcpy(out, b->d_state.get() + s, sizeof(LhStreamState), hipMemcpyDeviceToHost));
+    return (int) sizeof(LhStreamState);
+}
+
+/* host bit packing of one stream from its frames (already on the host) */
+static long
+pack_stream(const lamehip_batch * b, int s, const LhFrameOut * fr, int n, unsigned char *out, long out_size)
+{
+    LhBitstream bs;
+    long    pos = 0;
+    if (lh_bs_init(&bs) != 0)
+        return -2;
+    for (int i = 0; i < n; i++) {
+        int     k;
+        if (lh_bs_format_frame(&bs, &b->cfg, b->tab, &fr[i]) != 0) {
+            snprintf(g_err, sizeof(g_err), "inconsistent device payload (packer check %d) stream %d frame %d",
+                     bs.error, s, i);
+            lh_bs_free(&bs);
+            return LAMEHIP_ERR_PAYLOAD;
+        }
+        if (lh_bs_pending(&bs) > out_size - pos) {
+            lh_bs_free(&bs);
+            return -1;
+        }
+        k = lh_bs_copy(&bs, out + pos, 0);
+        pos += k;
+    }
+    lh_bs_flush(&bs, &b->cfg, n > 0 ? &fr[n - 1] : nullptr);
+    {
+        int     k;
+        if (lh_bs_pending(&bs) > out_size - pos) {
+            lh_bs_free(&bs);
+            return -1;
+        }
+        k = lh_bs_copy(&bs, out + pos, 0);
+        pos += k;
+    }
+    lh_bs_free(&bs);
+    return pos;
+}
+
+extern "C" long
+lamehip_batch_pack(lamehip_batch * b, int s, unsigned char *out, long out_size)
+{
+    std::vector < LhFrameOut > fr;
+    int     n;
+    if (!b || s < 0 || s >= b->B || !b->encoded)
+        return -1;
+    n = b->nframes[(size_t) s];
+    fr.resize((size_t) n);
+    if (lamehip_batch_get_frames(b, s, fr.data(), n) != n)
+        return LAMEHIP_ERR_DEVICE;
+    return pack_stream(b, s, fr.data(), n, out, out_size);
+}
+
+/* One stream as a complete file image: the final Xing/Info + LAME tag frame followed by the audio
+ * frames (what the reference's frontend leaves on disk after lame_mp3_tags_fid).  When the tag
+ * does not fit the frame size the audio alone is returned, as the reference would. */
+extern "C" long
+lamehip_batch_pack_tagged(lamehip_batch * b, int s, unsigned char *out, long out_size)
+{
+    LhVbrTag v;
+    std::vector < LhFrameOut > fr;
+    int     n, total;
+    long    k;
+    if (!b || s < 0 || s >= b->B || !b->encoded)
+        return -1;
+    total = lh_tag_init(&v, &b->cfg);
+    if (b->rate_in)
+        v.samplerate_in = b->rate_in;
+    if (out_size < total)
+        return -1;
+    n = b->nframes[(size_t) s];
+    fr.resize((size_t) n);
+    if (lamehip_batch_get_frames(b, s, fr.data(), n) != n)
+        return LAMEHIP_ERR_DEVICE;
+    k = pack_stream(b, s, fr.data(), n, out + total, out_size - total);
+    if (k < 0 || total == 0)
+        return k;
+    for (int i = 0; i < n; i++)
+        lh_tag_add_frame(&v, lh_tag_kbps(b->cfg.version, fr[(size_t) i].bitrate_index));
+    lh_tag_crc(&v, out + total, k);
+    if (lh_tag_frame(&v, &b->cfg, b->cfg.vbr_q, batch_padding(b, s), n > 0 ? fr[(size_t) n - 1].mode_ext : 0,
+                     out, total) != total)
+        memset(out, 0, (size_t) total);         /* no frames: the reference leaves the placeholder */
+    return k + total;
+}
+
+/* All streams, `nthreads' host threads: thread t takes streams t, t + nthreads, ...; each copies
+ * a stream's payload D2H into its own pinned buffer and packs it (the packer is serial per
+ * stream -- reference bitstream.c -- but streams are independent).  Stream s is written at
+ * out + s * out_stride; sizes[s] = bytes, or a negative error code. */
+extern "C" int
+lamehip_batch_pack_all(lamehip_batch * b, int nthreads, unsigned char *out, long out_stride, long *sizes)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int     dev = 0, maxf = 0;
+    std::atomic < int >failed(0);
+    /* the first failure of any worker: its code and its message (g_err is per thread) reach the caller */
+    std::mutex first_lock;
+    int     first_code = 0;
+    char    first_text[sizeof(g_err)] = "";
+    if (!b || !b->encoded || !out || !sizes || out_stride <= 0)
+        return -1;
+    if (nthreads < 1)
+        nthreads = 1;
+    if (nthreads > b->B)
+        nthreads = b->B;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    HIPCHK(hipGetDevice(&dev));
+    for (int s = 0; s < b->B; s++)
+        maxf = b->nframes[(size_t) s] > maxf ? b->nframes[(size_t) s] : maxf;
+    {
+        std::vector < std::thread > pool;
+        for (int t = 0; t < nthreads; t++)
+            pool.emplace_back([=, &failed, &first_lock, &first_code, &first_text] () {
+                auto note = [&](long code, const char *text) {
+                    std::lock_guard < std::mutex > hold(first_lock);
+                    if (first_code == 0) {
+                        first_code = (int) code;
+                        snprintf(first_text, sizeof(first_text), "%s", text);
+                    }
+                    failed = 1;
+                };
+                LhPinned < LhFrameOut > h;
+                LhStream st;
+                if (hipSetDevice(dev) != hipSuccess
+                    || h.alloc((size_t) (maxf > 0 ? maxf : 1)) != hipSuccess
+                    || st.create(hipStreamNonBlocking) != hipSuccess) {
+                    note(LAMEHIP_ERR_DEVICE, "pack_all: a worker could not set up its device staging");
+                    for (int s = t; s < b->B; s += nthreads)
+                        sizes[s] = LAMEHIP_ERR_DEVICE;
+                    return;
+                }
+                for (int s = t; s < b->B; s += nthreads) {
+                    int const n = b->nframes[(size_t) s];
+                    long    r;
+                    if (n > 0 && (hipMemcpyAsync(h.get(), b->d_out.get() + b->out_off[(size_t) s], (size_t) n * sizeof(LhFrameOut),
+                                                 hipMemcpyDeviceToHost, st) != hipSuccess
+                                  || hipStreamSynchronize(st) != hipSuccess))
+                    {
+                        r = LAMEHIP_ERR_DEVICE;
+                        snprintf(g_err, sizeof(g_err), "pack_all: copying stream %d's frames from the device failed", s);
+                    }
+                    else
+                        r = pack_stream(b, s, h.get(), n, out + (size_t) s * (size_t) out_stride, out_stride);
+                    sizes[s] = r;
+                    if (r < 0) {
+                        if (r == -1)
+                            snprintf(g_err, sizeof(g_err), "pack_all: out_stride %ld is too small for stream %d", out_stride, s);
+                        note(r, g_err);
+                    }
+                }
+            });
+        for (auto & th:pool)
+            th.join();
+    }
+    if (failed) {
+        snprintf(g_err, sizeof(g_err), "%s", first_text);
+        return first_code;
+    }
+    return 0;
+}

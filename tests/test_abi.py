@@ -92,3 +92,25 @@ def test_error_callback_receives_failures():
     lib.lame_set_out_samplerate(h, 20000)
     assert lib.lame_init_params(h) < 0 and len(seen) == 1
     lib.lame_close(h)
+
+
+def test_last_error_is_one_buffer_per_thread_across_the_api_files():
+    """lamehip_last_error() (lh_api.cpp) returns what the batch API (lh_batch.cpp) wrote, in the thread that made the
+    failed call and in no other."""
+    import threading
+    lib = lamehip.load_library()
+    lib.lamehip_batch_create_on.restype = C.c_void_p
+    lib.lamehip_batch_create_on.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_long]
+    assert lib.lamehip_batch_create_on(1 << 20, None, 1, 1) is None
+    assert lamehip.last_error() == "lamehip_batch_create_on: no HIP device 1048576"
+    seen = []
+
+    def worker():
+        seen.append(lamehip.last_error())
+        seen.append(lib.lamehip_batch_create_on(1 << 19, None, 1, 1))
+        seen.append(lamehip.last_error())
+    t = threading.Thread(target=worker)
+    t.start()
+    t.join()
+    assert seen == ["", None, "lamehip_batch_create_on: no HIP device 524288"]
+    assert lamehip.last_error() == "lamehip_batch_create_on: no HIP device 1048576"

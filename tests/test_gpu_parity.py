@@ -2,6 +2,7 @@
 C ABI of liblamehip.so; the checkers are the committed golden vectors, the CPU
 oracle and -- when it travelled with the tree -- the compiled reference."""
 import ctypes as C
+import functools
 import hashlib
 import os
 
@@ -1089,3 +1090,113 @@ def test_incremental_batch_lifecycle_and_large_chunks():
         b.reset()
     b.close()
     enc.close()
+
+
+REGROW_SECONDS = (0.25, 1.5, 0.25)      # per round: the second outgrows what the first allocated, the third fits again
+
+
+def _regrow_streams(rate, rnd):
+    n = int(rate * REGROW_SECONDS[rnd])
+    return [helpers.synth_stream(9100 + 10 * rnd + i, k, rate) for i, k in enumerate((n, n - 777, n // 2))]
+
+
+def _device_packed_batch(enc, nstreams, cap, resample):
+    b = lamehip.Batch(enc, nstreams, cap)
+    b.set_device_packing()
+    if resample:
+        b.set_device_resampling()
+    return b
+
+
+def _encode_and_fetch(b, pcms):
+    """through the pinned mirror, asynchronously, and back through the pinned byte buffer"""
+    h = b.pcm_host()
+    for s, x in enumerate(pcms):
+        h[s, :, :x.shape[1]] = x
+        b.set_length(s, x.shape[1])
+        b.mark_pcm(s)
+    b.encode(sync=False)
+    b.fetch()
+    return [bytes(b.bytes_view(s)) for s in range(len(pcms))]
+
+
+@functools.lru_cache(maxsize=None)
+def _regrow_reference(rate):
+    """per round: the bytes of a fresh batch given that round's streams (computed once per input rate)"""
+    enc = lamehip.Encoder(rate, out_samplerate=44100, brate=128)
+    want = []
+    for rnd in range(len(REGROW_SECONDS)):
+        f = _device_packed_batch(enc, 3, 2 * rate, rate != 44100)
+        want.append(_encode_and_fetch(f, _regrow_streams(rate, rnd)))
+        f.close()
+    enc.close()
+    return want
+
+
+def _lifecycle_bytes(kind):
+    """one batch of `kind' from creation to close: its streams' bytes"""
+    rate = 48000 if kind == "device-resampling" else 44100
+    pcms = [helpers.synth_stream(9200 + i, rate // 2 - 333 * i, rate) for i in range(2)]
+    enc = lamehip.Encoder(rate, out_samplerate=44100, brate=128)
+    if kind == "pipelined":
+        b = _device_packed_batch(enc, 2, rate // 2, False)
+        out = _encode_and_fetch(b, pcms)
+    elif kind == "incremental":
+        b = lamehip.Batch(enc, 2, rate // 2)
+        out = [b"", b""]
+        for at in range(0, rate // 2, 1000):
+            for s, x in enumerate(pcms):
+                b.append(s, x[0, at:at + 1000], x[1, at:at + 1000])
+            b.encode_available()
+            for s in range(2):
+                out[s] += b.drain(s)
+        b.finish()
+        for s in range(2):
+            out[s] += b.drain(s)
+    else:
+        b = lamehip.Batch(enc, 2, rate // 2)
+        if kind == "device-resampling":
+            b.set_device_resampling()
+        for s, x in enumerate(pcms):
+            b.set_pcm(s, x[0], x[1])
+        b.encode()
+        out = [b.pack(s) for s in range(2)]
+    b.close()
+    enc.close()
+    assert all(len(x) > 0 for x in out), kind
+    return out
+
+
+@pytest.mark.gpu
+def test_batch_buffers_regrow_on_a_live_batch_and_lifecycles_repeat(monkeypatch):
+    """What the batch's resource handling can get wrong without any kernel being involved.
+
+    Regrow: one device-packed batch of 3 streams (capacity 2 s) through rounds of 0.25 s, 1.5 s and 0.25 s streams -- the
+    second round outgrows the payload pool, the byte pool, its pinned mirror and the analysis pool of a batch that has
+    work behind it.  Every round's bytes equal a fresh batch's and the host packer's from the same frames.  The same for
+    a 48 -> 44.1 kHz batch that converts on the device (the conversion plan's buffers grow behind the stream's work) and
+    for launches in windows of 3 frames (the windows' descriptors and events grow).
+
+    Lifecycle: create, use, close, three times over, for a plain, a pipelined device-packed, a device-resampling and an
+    incremental batch: identical bytes every time, and lamehip_last_error() stays empty."""
+    for rate, window in ((44100, None), (48000, None), (44100, "3")):
+        if window:
+            monkeypatch.setenv("LAMEHIP_MID_WINDOW", window)
+        want = _regrow_reference(44100 if window else rate)
+        enc = lamehip.Encoder(rate, out_samplerate=44100, brate=128)
+        b = _device_packed_batch(enc, 3, 2 * rate, rate != 44100)
+        for rnd in range(len(REGROW_SECONDS)):
+            got = _encode_and_fetch(b, _regrow_streams(rate, rnd))
+            assert b.windows() == (1 if not window else -(-max(b.frames(s) for s in range(3)) // 3)), (rate, window, rnd)
+            for s in range(3):
+                assert got[s] == want[rnd][s], (rate, window, rnd, s, "fresh batch")
+                assert got[s] == b.pack(s), (rate, window, rnd, s, "host packer")
+        b.close()
+        enc.close()
+        monkeypatch.delenv("LAMEHIP_MID_WINDOW", raising=False)
+    for kind in ("plain", "pipelined", "device-resampling", "incremental"):
+        cycles = []
+        for _ in range(3):
+            cycles.append(_lifecycle_bytes(kind))
+            assert lamehip.last_error() == "", (kind, lamehip.last_error())
+        assert cycles[0] == cycles[1] == cycles[2], kind

@@ -4,7 +4,9 @@
 set -e
 cd "$(dirname "$0")/../deprecated-lame-mirror_amd/csrc"
 make -s -j8 all
-OBJS="lh_kernels.o lh_kernels_vbr.o lh_kernels_lsf.o lh_kernels_q_vbr.o lh_kernels_q_lsf.o lh_analysis.o lh_analysis_lsf.o lh_subband.o lh_subband_lsf.o lh_api.o lh_host_init.o lh_bitstream.o lh_vbrtag.o lh_resample.o lh_replaygain.o"
+# (the product's objects, as the Makefile lists them, without lh_kernels_q.o)
+OBJS=" $(make -s print-KERNELS) $(make -s print-FRONT) $(make -s print-HOST) "
+OBJS=${OBJS/ lh_kernels_q.o / }
 for spec in "$@"; do
   name=${spec%%:*}; flags=${spec#*:}
   ( /opt/rocm/bin/hipcc --offload-arch=gfx950 $flags -std=c++17 -fno-fast-math -ffp-contract=off -fPIC -I. -I../../include -DLH_SPLIT -c lh_kernels.hip -o /tmp/lh_kernels_q_$name.o &&
