@@ -205,13 +205,13 @@ lh_wave_max8(const uint32_t (&v)[8])
     return t[lh_lane() & 7];
 }
 
-/* value of lane - n (0 where there is none); n = 1, 2, 3 */
+/* value of lane - n inside a row of 16 lanes (0 where there is none); n = 1, 2, 3: the device's row_shr */
 template < int N > static inline uint32_t
 lh_lane_minus_u32(uint32_t v)
 {
     const uint64_t *x = hipemu_wave_exchange(v);
     int const me = lh_lane();
-    return me >= N ? (uint32_t) x[me - N] : 0u;
+    return (me & 15) >= N ? (uint32_t) x[me - N] : 0u;
 }
 
 /* value of lane - D of the same row of 16 lanes (0 where there is none): the device's row_shr */
@@ -223,13 +223,13 @@ lh_row_shr_u32(uint32_t v)
     return (me & 15) >= D ? (uint32_t) x[me - D] : 0u;
 }
 
-/* value of the lane below (0 for lane 0) */
+/* value of the lane below inside a row of 16 lanes (0 for the row's first lane, as on the device) */
 static inline uint32_t
 lh_lane_below_u32(uint32_t v)
 {
     const uint64_t *x = hipemu_wave_exchange(v);
     int const me = lh_lane();
-    return me > 0 ? (uint32_t) x[me - 1] : 0u;
+    return (me & 15) > 0 ? (uint32_t) x[me - 1] : 0u;
 }
 
 /* value of the lane above; lane 63 gets lane 0's value of `next' (the wave's next slot of a striped array) */

@@ -23,6 +23,7 @@ expression literally.  Each is checked here exhaustively over the domain the ker
 import numpy as np
 
 import helpers  # noqa: F401  (puts the package on sys.path)
+import identity_support
 
 
 def test_float_addition_equals_the_double_rounding_for_every_quantisable_float():
@@ -102,40 +103,17 @@ def test_far_masking_rule_without_the_quotient():
     mid_i2 = float(enc.tables().mask_mid[9])
     enc.close()
     rng = np.random.default_rng(11)
-    cs += [np.float32(v) for v in (1.0000001, 1.5, 3.1622777, 31.622776, 1000.0)]
-    cs += list(rng.uniform(1.0, 100.0, 8).astype(np.float32))
+    cs += identity_support.far_other_constants(rng)
     with np.errstate(over="ignore", divide="ignore", invalid="ignore", under="ignore"):
         for c in cs:
-            below = (np.array([c], np.float32).view(np.uint32) - np.uint32(1)).view(np.float32)[0]
-            bound = 0.5 * (np.float64(c) + np.float64(below))
+            bound = identity_support.boundary(c)
             if c == cs[0]:
                 assert bound == mid_i2      # what the kernel reads (LhTables.mask_mid[9])
             # smaller: every exponent (denormals included) with random mantissas; larger: c x smaller +- 0..40 ulps
-            expo = np.repeat(np.arange(0, 254, dtype=np.uint32), 4000)
-            lo = ((expo << 23) | rng.integers(0, 1 << 23, expo.size, dtype=np.uint32)).view(np.float32)
-            base = (c * lo).astype(np.float32)
-            ok = np.isfinite(base)
-            lo, base = lo[ok], base[ok]
-            hi = (base.view(np.uint32).astype(np.int64) + rng.integers(-40, 41, base.size)).clip(0, 0x7f7fffff).astype(np.uint32).view(np.float32)
-            lo2 = rng.random(2_000_000, dtype=np.float32) * np.float32(1e6)
-            hi2 = lo2 * (rng.random(2_000_000, dtype=np.float32) * np.float32(2.0) * c)
-            lo = np.concatenate([lo, lo2, np.zeros(4, np.float32)])
-            hi = np.concatenate([hi, hi2, np.array([0, 1, 1e-40, 3e38], np.float32)])
-            hi, lo = np.maximum(hi, lo), np.minimum(hi, lo)
-            ref = np.where(lo > 0, (hi / lo).astype(np.float32) < c, False)
+            hi, lo = identity_support.far_pairs(rng, c)
+            ref = identity_support.far_reference(hi, lo, c)
             mine = hi.astype(np.float64) < bound * lo.astype(np.float64)
             assert np.array_equal(ref, mine), c
-
-
-def _mask_cell(log_table, ratio):
-    """the reference's table cell for float ratios >= 1 (util.c:976-1001, psymodel.c:331)"""
-    bits = ratio.view(np.uint32)
-    mant = (bits & np.uint32(0x7fffff)).astype(np.int32)
-    whole = (((bits >> np.uint32(23)) & np.uint32(0xff)).astype(np.int32) - 0x7f).astype(np.float32)
-    along = (mant & 16383).astype(np.float32) * np.float32(1.0 / 16384)
-    slot = mant >> 14
-    lg = whole + (log_table[slot] * (np.float32(1.0) - along) + log_table[slot + 1] * along)
-    return (lg.astype(np.float64) * (np.float64(0.69314718055994530942 / 2.30258509299404568402) * np.float64(16.0))).astype(np.int32)
 
 
 def test_near_masking_rule_without_quotient_or_logarithm():
@@ -146,44 +124,21 @@ def test_near_masking_rule_without_quotient_or_logarithm():
     mid = np.ctypeslib.as_array(T.mask_mid).astype(np.float64)
     c1 = np.float32(T.ma_max_i1)
     enc.close()
-    table2 = np.array([1.33352 ** 2, 1.35879 ** 2, 1.38454 ** 2, 1.39497 ** 2, 1.40548 ** 2, 1.3537 ** 2, 1.30382 ** 2,
-                       1.22321 ** 2, 1.14758 ** 2, 1.0]).astype(np.float32)       # psymodel.c:297-302
-
-    def boundary(v):
-        below = (np.array([v], np.float32).view(np.uint32) - np.uint32(1)).view(np.float32)[0]
-        return 0.5 * (np.float64(v) + np.float64(below))
-
+    table2 = identity_support.TABLE2
+    boundary = identity_support.boundary
     # every float ratio in [1, ma_max_i1): cells 0..8, never decreasing, stepping where the host says
-    lo_b, hi_b = int(np.float32(1.0).view(np.uint32)), int(c1.view(np.uint32))
-    ratio = np.arange(lo_b, hi_b, dtype=np.uint32).view(np.float32)
-    cell = _mask_cell(log_table, ratio)
-    assert cell[0] == 0 and cell[-1] == 8 and np.all(np.diff(cell) >= 0)
-    steps = ratio[1:][np.diff(cell) != 0]
+    first, last, monotone, steps = identity_support.near_walk(log_table, c1)
+    assert first == 0 and last == 8 and monotone
     assert len(steps) == 8
     assert np.array_equal(np.array([boundary(r) for r in steps]), mid[:8])
     assert mid[8] == boundary(c1)
     # the whole rule on pairs around every boundary and on random pairs
     rng = np.random.default_rng(12)
     with np.errstate(over="ignore", divide="ignore", invalid="ignore", under="ignore"):
-        los, his = [], []
-        for r in list(steps) + [c1]:
-            expo = np.repeat(np.arange(0, 250, dtype=np.uint32), 800)
-            lo = ((expo << 23) | rng.integers(0, 1 << 23, expo.size, dtype=np.uint32)).view(np.float32)
-            base = (np.float32(r) * lo).astype(np.float32)
-            ok = np.isfinite(base)
-            lo, base = lo[ok], base[ok]
-            hi = (base.view(np.uint32).astype(np.int64) + rng.integers(-40, 41, base.size)).clip(0, 0x7f7fffff).astype(np.uint32).view(np.float32)
-            los.append(lo)
-            his.append(hi)
-        lo2 = rng.random(3_000_000, dtype=np.float32) * np.float32(1e6)
-        los += [lo2, np.zeros(4, np.float32)]
-        his += [lo2 * (rng.random(3_000_000, dtype=np.float32) * np.float32(5.0)), np.array([0, 1, 1e-40, 3e38], np.float32)]
-        a, b = np.concatenate(his), np.concatenate(los)
+        a, b = identity_support.near_pairs(rng, steps, c1)
         hi, lo = np.maximum(a, b), np.minimum(a, b)
         total = a + b
-        q = (hi / np.where(lo > 0, lo, np.float32(1.0))).astype(np.float32)
-        safe = np.where((lo > 0) & (q < c1), q, np.float32(1.0))
-        ref = np.where(lo > 0, np.where(q >= c1, total, total * table2[_mask_cell(log_table, safe)]), hi)
+        ref = identity_support.near_reference(log_table, c1, a, b)
         count = np.zeros(hi.size, np.int64)
         for j in range(9):
             count += hi.astype(np.float64) > mid[j] * lo.astype(np.float64)
