@@ -9,6 +9,15 @@
 #include <atomic>
 
 #include "lh_api_int.h"
+#include "lh_pcm_in.h"
+
+extern "C" int lh_launch_resample_typed(int type, const LhRsParams * p, const float *bank, const LhRsBlock * trunk, const LhRsBlock * tails,
+                                        const LhRsStream * streams, int nstreams, int max_blocks, const void *pcm, float *pcmf,
+                                        void *stream);
+extern "C" int lh_launch_ingest(int type, const LhInParams * p, const LhInStream * streams, int nstreams, long long max_n, const void *in,
+                                float *out, void *stream);
+extern "C" int lh_launch_deinterleave(int esz, const void *src_l, const void *src_r, void *dst_l, void *dst_r, long long n, void *stream);
+extern "C" void lh_pcm_copy_plane(void *dst, const void *src, int esz, int stride, long n);
 
 /* per device: the end of the last launch that filled it (lamehip_batch_encode) */
 static LhLaunchSerial &
@@ -49,7 +58,19 @@ struct lamehip_batch {
     LhDeviceConst dc;
     int     B = 0;
     long    cap = 0;
-    LhDevBuf < int16_t > d_pcm; /* [B][2][cap] */
+    LhDevBuf < int16_t > d_pcm; /* [B][2][cap] elements of esz bytes (held in units of two bytes) */
+    /* the sample type of the input pool and of its pinned mirror (lamehip_batch_set_sample_type): other than s16 the pool
+     * holds int32 or float, the kernels read the float pool d_pcmf ([B][2][cap] when the batch does not convert the rate),
+     * and lamehip_batch_encode fills that from the pool with lh_ingest.hip -- or with the rate converter, which then reads
+     * the typed pool -- for the streams declared since their last ingest */
+    int     stype = LH_PCM_S16;
+    int     esz = 2;
+    std::vector < char >in_dirty;
+    std::vector < LhInStream > h_in_streams;
+    LhDevBuf < LhInStream > d_in_streams;
+    LhEvent ev_in[2];
+    int     in_ran = 0;         /* the last lamehip_batch_encode ingested something (between ev_in[0] and ev_in[1]) */
+    float   in_ms = 0;
     LhDevBuf < LhStreamState > d_state;
     LhDevBuf < LhStreamState > d_state0;        /* the streams' initial states (batch_reset_states) */
     LhDevBuf < LhStreamDesc > d_desc;
@@ -352,6 +373,33 @@ batch_padding(const lamehip_batch * b, int s)
     return b->rate_in ? b->padding[(size_t) s] : lh_end_padding_fs(b->len[(size_t) s], fs_of(b->cfg));
 }
 
+/* the kernels of this batch read the float pool */
+static int
+batch_reads_floats(const lamehip_batch * b)
+{
+    return b->rate_in || b->stype != LH_PCM_S16;
+}
+
+/* row ch of stream s in the input pool / in its pinned mirror */
+static unsigned char *
+batch_pool_row(const lamehip_batch * b, int s, int ch)
+{
+    return (unsigned char *) b->d_pcm.get() + ((size_t) s * 2 + (size_t) ch) * (size_t) b->cap * (size_t) b->esz;
+}
+
+static unsigned char *
+batch_mirror_row(const lamehip_batch * b, int s, int ch)
+{
+    return (unsigned char *) b->h_pcm.get() + ((size_t) s * 2 + (size_t) ch) * (size_t) b->cap * (size_t) b->esz;
+}
+
+/* bytes of the whole input pool */
+static size_t
+batch_pool_bytes(const lamehip_batch * b)
+{
+    return (size_t) b->B * 2 * (size_t) b->cap * (size_t) b->esz;
+}
+
 /* every stream back to its initial state: a device-to-device copy of the pristine image on the batch's own
  * stream (a host copy on the null stream would wait for every other batch's work in flight) */
 static int
@@ -512,15 +560,17 @@ batch_len_in(const lamehip_batch * b, int s)
 extern "C" int
 lamehip_batch_set_length(lamehip_batch * b, int s, long n)
 {
-    if (!b || s < 0 || s >= b->B || n < 0 || (n > b->cap && !b->dev_rs) || (b->rate_in && !b->dev_rs))
+    if (!b || s < 0 || s >= b->B || n < 0 || (b->rate_in && !b->dev_rs))
         return -1;              /* (a batch that converts on the host needs the samples themselves: lamehip_batch_set_pcm) */
-    if (b->dev_rs && n > b->cap) {
+    if (n > b->cap) {
         snprintf(g_err, sizeof(g_err), "lamehip_batch_set_length: stream of %ld samples exceeds the pool (%ld per stream)", n, b->cap);
         return -1;
     }
     b->pcm_given = 1;
     if (b->dev_rs)
         return batch_plan_stream(b, s, n);
+    if (b->stype != LH_PCM_S16)
+        b->in_dirty[(size_t) s] = 1;    /* declared: the stream is ingested again */
     b->len[(size_t) s] = n;
     b->nframes[(size_t) s] = lh_total_frames_fs(n, fs_of(b->cfg));
     return 0;
@@ -562,7 +612,6 @@ batch_convert_stream(lamehip_batch * b, int s, const short *l, const short *r, l
     return 0;
 }
 
-extern "C" short *lamehip_batch_pcm_host_ptr(lamehip_batch * b);
 
 /* the mirror for lamehip_batch_set_pcm: made on first use unless the pool is larger than LAMEHIP_PINNED_MAX_MB
  * (default 4096) of pinned host memory */
@@ -572,9 +621,9 @@ batch_host_pool(lamehip_batch * b)
     if (!b->h_pcm.get() && (!b->rate_in || b->dev_rs)) {
         const char *e = getenv("LAMEHIP_PINNED_MAX_MB");
         double const limit = (e ? atof(e) : 4096.0) * 1048576.0;
-        if ((double) b->B * 4.0 * (double) b->cap > limit)
+        if ((double) batch_pool_bytes(b) > limit)
             return nullptr;
-        (void) lamehip_batch_pcm_host_ptr(b);
+        (void) lamehip_batch_input_host_ptr(b);
     }
     return b->h_pcm.get();
 }
@@ -595,6 +644,10 @@ extern "C" int
 lamehip_batch_set_pcm(lamehip_batch * b, int s, const short *l, const short *r, long n)
 {
     LhDeviceScope const on_device(b ? b->device : -1);
+    if (b && b->stype != LH_PCM_S16) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_pcm: this batch's sample type is not s16 (lamehip_batch_set_input takes its samples)");
+        return -1;
+    }
     if (b && b->rate_in && !b->dev_rs) {
         if (s < 0 || s >= b->B || n < 0)
             return -1;
@@ -629,13 +682,13 @@ lamehip_batch_set_pcm(lamehip_batch * b, int s, const short *l, const short *r, 
 /* The pinned mirror of the batch's s16 pool, [stream][2][capacity] like the pool itself: the caller may
  * decode straight into it (then lamehip_batch_set_length + lamehip_batch_mark_pcm, or lamehip_batch_set_pcm,
  * which copies into it).  NULL for a converting batch or when the mirror cannot be had. */
-extern "C" short *
-lamehip_batch_pcm_host_ptr(lamehip_batch * b)
+extern "C" void *
+lamehip_batch_input_host_ptr(lamehip_batch * b)
 {
     LhDeviceScope const on_device(b ? b->device : -1);
     if (!b)
         return nullptr;
-    if (!b->h_pcm.get() && (!b->rate_in || b->dev_rs) && b->h_pcm.alloc((size_t) b->B * 2 * (size_t) b->cap) != hipSuccess)
+    if (!b->h_pcm.get() && (!b->rate_in || b->dev_rs) && b->h_pcm.alloc(batch_pool_bytes(b) / sizeof(int16_t)) != hipSuccess)
         (void) hipGetLastError();
     /* whoever asks for the pointer is about to write through it: no upload may still be reading the mirror.  (A caller
      * that keeps the pointer across rounds asks again -- or calls lamehip_batch_set_pcm -- before it rewrites rows that
@@ -647,6 +700,17 @@ lamehip_batch_pcm_host_ptr(lamehip_batch * b)
     return b->h_pcm.get();
 }
 
+/* the mirror of an s16 batch as shorts; NULL for any other sample type (lamehip_batch_input_host_ptr) */
+extern "C" short *
+lamehip_batch_pcm_host_ptr(lamehip_batch * b)
+{
+    if (b && b->stype != LH_PCM_S16) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_pcm_host_ptr: this batch's sample type is not s16 (lamehip_batch_input_host_ptr)");
+        return nullptr;
+    }
+    return (short *) lamehip_batch_input_host_ptr(b);
+}
+
 /* stream s's rows of the mirror were written by the caller: they travel with the next upload */
 extern "C" int
 lamehip_batch_mark_pcm(lamehip_batch * b, int s)
@@ -655,6 +719,8 @@ lamehip_batch_mark_pcm(lamehip_batch * b, int s)
         return -1;
     if (b->dev_rs)
         b->rs_dirty[(size_t) s] = 1;    /* new samples: the stream is converted again */
+    else if (b->stype != LH_PCM_S16)
+        b->in_dirty[(size_t) s] = 1;    /* ... or ingested again */
     if (!b->row_dirty[(size_t) s]) {
         b->row_dirty[(size_t) s] = 1;
         b->n_dirty++;
@@ -696,16 +762,14 @@ lamehip_batch_upload(lamehip_batch * b)
         for (int s = 0; s < b->B; s++)
             used += batch_len_in(b, s);
         if (b->n_dirty == b->B && used * 10 >= (long long) b->B * b->cap * 9)
-            HIPCHK(hipMemcpyAsync(b->d_pcm.get(), b->h_pcm.get(), (size_t) b->B * 2 * (size_t) b->cap * 2, hipMemcpyHostToDevice, b->up_stream));
+            HIPCHK(hipMemcpyAsync(b->d_pcm.get(), b->h_pcm.get(), batch_pool_bytes(b), hipMemcpyHostToDevice, b->up_stream));
         else
             for (int s = 0; s < b->B; s++) {
-                size_t const n = (size_t) batch_len_in(b, s) * 2;
+                size_t const n = (size_t) batch_len_in(b, s) * (size_t) b->esz;
                 if (!b->row_dirty[(size_t) s] || n == 0)
                     continue;
-                for (int ch = 0; ch < 2; ch++) {
-                    size_t const at = ((size_t) s * 2 + (size_t) ch) * (size_t) b->cap;
-                    HIPCHK(hipMemcpyAsync(b->d_pcm.get() + at, b->h_pcm.get() + at, n, hipMemcpyHostToDevice, b->up_stream));
-                }
+                for (int ch = 0; ch < 2; ch++)
+                    HIPCHK(hipMemcpyAsync(batch_pool_row(b, s, ch), batch_mirror_row(b, s, ch), n, hipMemcpyHostToDevice, b->up_stream));
             }
     }
     HIPCHK(hipEventRecord(b->ev_up, b->up_stream));
@@ -716,10 +780,105 @@ lamehip_batch_upload(lamehip_batch * b)
     return 0;
 }
 
+/* Samples of the batch's own type from host buffers: l and r advance by `stride' elements per sample (1: planar; 2:
+ * interleaved, r = l + 1, as lame_encode_buffer_interleaved* is called).  What lamehip_batch_set_pcm does for shorts. */
+extern "C" int
+lamehip_batch_set_input(lamehip_batch * b, int s, const void *l, const void *r, int stride, long n)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b || s < 0 || s >= b->B || n < 0 || (stride != 1 && stride != 2)) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_input: no such stream, a negative length or a stride other than 1 or 2");
+        return -1;
+    }
+    bool const one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
+    if (one_plane)
+        r = l;                  /* mono: the second plane mirrors the first, the kernel never uses it */
+    if (n > 0 && (!l || !r))
+        return -1;
+    if (b->rate_in && !b->dev_rs) {
+        /* (a batch that converts on the host is s16: lamehip_batch_set_sample_type) */
+        std::vector < short >tl((size_t) n + 1), tr((size_t) n + 1);
+        lh_pcm_copy_plane(tl.data(), l, 2, stride, n);
+        lh_pcm_copy_plane(tr.data(), r, 2, stride, n);
+        return lamehip_batch_set_pcm(b, s, tl.data(), tr.data(), n);
+    }
+    if (lamehip_batch_set_length(b, s, n) != 0)
+        return -1;
+    if (batch_host_pool(b) != nullptr) {
+        if (batch_mirror_quiesce(b) != 0)
+            return LAMEHIP_ERR_DEVICE;
+        lh_pcm_copy_plane(batch_mirror_row(b, s, 0), l, b->esz, stride, n);
+        lh_pcm_copy_plane(batch_mirror_row(b, s, 1), r, b->esz, stride, n);
+        if (!b->row_dirty[(size_t) s]) {
+            b->row_dirty[(size_t) s] = 1;
+            b->n_dirty++;
+        }
+        return 0;
+    }
+    /* the pool is too large to mirror in pinned memory: straight to HBM, stream by stream */
+    std::vector < unsigned char >tmp;
+    for (int ch = 0; ch < 2; ch++) {
+        const void *src = ch ? r : l;
+        if (stride != 1) {
+            tmp.resize((size_t) n * (size_t) b->esz + 1);
+            lh_pcm_copy_plane(tmp.data(), src, b->esz, stride, n);
+            src = tmp.data();
+        }
+        if (n > 0)
+            HIPCHK(hipMemcpy(batch_pool_row(b, s, ch), src, (size_t) n * (size_t) b->esz, hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+/* the same from buffers in HBM, synchronous: stride 1 is two device-to-device copies, stride 2 a kernel that takes the
+ * interleaved buffer apart (lh_ingest.hip) */
+extern "C" int
+lamehip_batch_set_input_device(lamehip_batch * b, int s, const void *dl, const void *dr, int stride, long n)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (b && stride != 1 && stride != 2) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_input_device: stride %d (1: planar, 2: interleaved)", stride);
+        return -1;
+    }
+    if (lamehip_batch_set_length(b, s, n) != 0)
+        return -1;
+    bool const one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
+    if (one_plane)
+        dr = dl;
+    if (n > 0 && (!dl || !dr))
+        return -1;
+    if (b->up_pending || b->up_inflight) {      /* an upload of the mirror is on its way into the same pool */
+        HIPCHK(hipStreamSynchronize(b->up_stream));
+        b->up_inflight = 0;
+    }
+    if (b->row_dirty[(size_t) s]) {     /* what the mirror holds for this stream is superseded */
+        b->row_dirty[(size_t) s] = 0;
+        b->n_dirty--;
+    }
+    if (n == 0)
+        return 0;
+    if (stride == 1) {
+        HIPCHK(hipMemcpy(batch_pool_row(b, s, 0), dl, (size_t) n * (size_t) b->esz, hipMemcpyDeviceToDevice));
+        HIPCHK(hipMemcpy(batch_pool_row(b, s, 1), dr, (size_t) n * (size_t) b->esz, hipMemcpyDeviceToDevice));
+        return 0;
+    }
+    /* (on the batch's stream: behind a kernel of the previous round that may still be reading the pool) */
+    int const rc = lh_launch_deinterleave(b->esz, dl, dr, batch_pool_row(b, s, 0), one_plane ? nullptr : batch_pool_row(b, s, 1),
+                                          n, (void *) (hipStream_t) b->stream);
+    if (rc)
+        return set_err("de-interleave launch", (hipError_t) rc);
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return 0;
+}
+
 extern "C" int
 lamehip_batch_set_pcm_device(lamehip_batch * b, int s, const void *dl, const void *dr, long n)
 {
     LhDeviceScope const on_device(b ? b->device : -1);
+    if (b && b->stype != LH_PCM_S16) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_pcm_device: this batch's sample type is not s16 (lamehip_batch_set_input_device)");
+        return -1;
+    }
     if (lamehip_batch_set_length(b, s, n) != 0)
         return -1;
     if (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f)
@@ -756,6 +915,10 @@ batch_incremental_begin(lamehip_batch * b)
 {
     if (b->incremental)
         return 0;
+    if (b->stype != LH_PCM_S16) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_append: incremental batches are s16, this batch's sample type is not (lamehip_batch_set_input)");
+        return -1;
+    }
     if (b->rate_in || b->dev_pack) {
         snprintf(g_err, sizeof(g_err), "incremental batches take the encoder's own input rate and the host packer");
         return -1;
@@ -1108,7 +1271,8 @@ batch_convert_launch(lamehip_batch * b)
     LhRsParams p;
     memset(&p, 0, sizeof(p));
     p.ratio = b->rs->ratio;
-    p.m = lh_rs_matrix(b->cfg.pcm_scale, b->cfg.pcm_mix, b->cfg.pcm_scale_r);
+    p.m = b->stype != LH_PCM_S16 ? lh_pcm_matrix(b->stype, b->cfg.pcm_scale, b->cfg.pcm_mix, b->cfg.pcm_scale_r)
+        : lh_rs_matrix(b->cfg.pcm_scale, b->cfg.pcm_mix, b->cfg.pcm_scale_r);
     p.taps = b->rs->taps;
     p.phases = b->rs->phases;
     p.channels = b->cfg.channels;
@@ -1116,13 +1280,57 @@ batch_convert_launch(lamehip_batch * b)
     p.cap_in = b->cap;
     p.cap_out = b->capf;
     HIPCHK(hipEventRecord(b->ev_rs[0], b->stream));
-    int const rc = lh_launch_resample(&p, b->d_rs_bank.get(), b->d_rs_trunk.get(), b->d_rs_tails.get(), b->d_rs_streams.get(), (int) b->h_rs_streams.size(),
-                                      max_blocks, b->d_pcm.get(), b->d_pcmf.get(), (void *) (hipStream_t) b->stream);
+    /* (a typed pool goes through the same kernel, its staging load in the pool's type: no ingest pass in between) */
+    int const rc = b->stype != LH_PCM_S16
+        ? lh_launch_resample_typed(b->stype, &p, b->d_rs_bank.get(), b->d_rs_trunk.get(), b->d_rs_tails.get(), b->d_rs_streams.get(),
+                                   (int) b->h_rs_streams.size(), max_blocks, b->d_pcm.get(), b->d_pcmf.get(), (void *) (hipStream_t) b->stream)
+        : lh_launch_resample(&p, b->d_rs_bank.get(), b->d_rs_trunk.get(), b->d_rs_tails.get(), b->d_rs_streams.get(), (int) b->h_rs_streams.size(),
+                             max_blocks, b->d_pcm.get(), b->d_pcmf.get(), (void *) (hipStream_t) b->stream);
     if (rc)
         return set_err("conversion launch", (hipError_t) rc);
     HIPCHK(hipEventRecord(b->ev_rs[1], b->stream));
     b->rs_ran = 1;
     b->rs_dirty.assign((size_t) b->B, 0);
+    return 0;
+}
+
+/* A typed batch that does not convert the rate: the streams declared since their last ingest go from the input pool into
+ * the float pool (lh_ingest.hip), on the batch's stream; the list travels first, then one launch. */
+static int
+batch_ingest_launch(lamehip_batch * b)
+{
+    long long max_n = 0;
+    b->in_ran = 0;
+    b->h_in_streams.clear();
+    for (int s = 0; s < b->B; s++) {
+        if (!b->in_dirty[(size_t) s] || b->len[(size_t) s] <= 0)
+            continue;
+        LhInStream d;
+        d.n = b->len[(size_t) s];
+        d.stream = s;
+        d.pad_ = 0;
+        b->h_in_streams.push_back(d);
+        if (d.n > max_n)
+            max_n = d.n;
+    }
+    b->in_dirty.assign((size_t) b->B, 0);
+    if (b->h_in_streams.empty())
+        return 0;
+    HIPCHK(hipMemcpyAsync(b->d_in_streams.get(), b->h_in_streams.data(), b->h_in_streams.size() * sizeof(LhInStream), hipMemcpyHostToDevice,
+                          b->stream));
+    LhInParams p;
+    memset(&p, 0, sizeof(p));
+    p.m = lh_pcm_matrix(b->stype, b->cfg.pcm_scale, b->cfg.pcm_mix, b->cfg.pcm_scale_r);
+    p.channels = b->cfg.channels;
+    p.one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
+    p.cap = b->cap;
+    HIPCHK(hipEventRecord(b->ev_in[0], b->stream));
+    int const rc = lh_launch_ingest(b->stype, &p, b->d_in_streams.get(), (int) b->h_in_streams.size(), max_n, b->d_pcm.get(), b->d_pcmf.get(),
+                                    (void *) (hipStream_t) b->stream);
+    if (rc)
+        return set_err("ingest launch", (hipError_t) rc);
+    HIPCHK(hipEventRecord(b->ev_in[1], b->stream));
+    b->in_ran = 1;
     return 0;
 }
 
@@ -1165,8 +1373,8 @@ lamehip_batch_encode(lamehip_batch * b)
     for (int s = 0; s < b->B; s++) {
         LhStreamDesc & d = b->h_desc[(size_t) s];
         b->out_off[(size_t) s] = total;
-        d.pcm_l = ((long long) s * 2) * (b->rate_in ? b->capf : b->cap);
-        d.pcm_r = ((long long) s * 2 + 1) * (b->rate_in ? b->capf : b->cap);
+        d.pcm_l = ((long long) s * 2) * (batch_reads_floats(b) ? b->capf : b->cap);
+        d.pcm_r = ((long long) s * 2 + 1) * (batch_reads_floats(b) ? b->capf : b->cap);
         d.pcm_base = 0;
         d.nsamples = b->len[(size_t) s];
         d.out_index = total;
@@ -1197,9 +1405,15 @@ lamehip_batch_encode(lamehip_batch * b)
     }
     HIPCHK(hipMemcpyAsync(b->d_desc.get(), b->h_desc.data(), (size_t) b->B * sizeof(LhStreamDesc),
                           hipMemcpyHostToDevice, b->stream));
-    /* device conversion: behind the upload wait, in front of the analysis kernels */
+    /* device conversion, or the ingest of a typed pool: behind the upload wait, in front of the analysis kernels */
+    b->in_ran = 0;
     if (b->dev_rs) {
         int const rc = batch_convert_launch(b);
+        if (rc)
+            return rc;
+    }
+    else if (b->stype != LH_PCM_S16) {
+        int const rc = batch_ingest_launch(b);
         if (rc)
             return rc;
     }
@@ -1223,7 +1437,8 @@ lamehip_batch_encode(lamehip_batch * b)
         int const big = (b->B >= 512);
         if (big && ser.ev)
             HIPCHK(hipStreamWaitEvent(b->stream, ser.ev, 0));
-        int     rc = batch_launch(b, b->rate_in ? (const int16_t *) 0 : b->d_pcm.get(), b->rate_in ? b->d_pcmf.get() : (const float *) 0,
+        int     rc = batch_launch(b, batch_reads_floats(b) ? (const int16_t *) 0 : b->d_pcm.get(),
+                                  batch_reads_floats(b) ? b->d_pcmf.get() : (const float *) 0,
                                   b->d_desc.get(), plan, b->dev_pack ? b->d_bytes.get() : (uint8_t *) 0);
         if (rc)
             return rc;
@@ -1333,6 +1548,10 @@ lamehip_batch_set_device_resampling(lamehip_batch * b, int on)
         snprintf(g_err, sizeof(g_err), "lamehip_batch_set_device_resampling: only before any PCM is handed over");
         return -1;
     }
+    if (!on && b->stype != LH_PCM_S16) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_device_resampling: the host converter takes s16 only, this batch's sample type is not");
+        return -1;
+    }
     if (!on || b->dev_rs) {
         b->dev_rs = on != 0 && b->dev_rs;
         return 0;
@@ -1378,15 +1597,78 @@ lamehip_batch_set_device_resampling(lamehip_batch * b, int on)
     return 0;
 }
 
-/* test accessor: the converted signal of stream s as the encoder reads it (after lamehip_batch_set_pcm when the host
- * converts, after lamehip_batch_encode when the device does); returns its length, or a negative code */
+/* The sample type of the input pool (LAMEHIP_PCM_*), only before any PCM is handed over.  Other than s16 the batch gets an
+ * input pool of that element type in place of the s16 pool and -- unless it converts the rate, which brings one -- a float
+ * pool of the same geometry for the kernels to read. */
+extern "C" int
+lamehip_batch_set_sample_type(lamehip_batch * b, int type)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b)
+        return -1;
+    if (type < 0 || type >= LH_PCM_TYPES) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_sample_type: no sample type %d", type);
+        return -1;
+    }
+    if (b->pcm_given || b->encoded || b->incremental) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_sample_type: only before any PCM is handed over");
+        return -1;
+    }
+    if (type != LH_PCM_S16 && b->rate_in && !b->dev_rs) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_sample_type: a batch that converts the sample rate on the host takes s16 only "
+                 "(lamehip_batch_set_device_resampling first)");
+        return -1;
+    }
+    if (type == b->stype)
+        return 0;
+    /* everything new first: a failure leaves the batch as it was */
+    int const esz = lh_pcm_elem_size(type);
+    bool const own_floats = (type != LH_PCM_S16 && !b->rate_in);
+    size_t const pool = (size_t) b->B * 2 * (size_t) b->cap * (size_t) esz;
+    LhDevBuf < int16_t > pcm;
+    LhDevBuf < float >pcmf;
+    LhDevBuf < LhInStream > streams;
+    LhEvent ev[2];
+    hipError_t e = pcm.alloc(pool / sizeof(int16_t));
+    if (e == hipSuccess && own_floats)
+        e = pcmf.alloc((size_t) b->B * 2 * (size_t) b->cap);
+    if (e == hipSuccess && own_floats)
+        e = streams.alloc((size_t) b->B);
+    if (e == hipSuccess && own_floats)
+        e = ev[0].create();
+    if (e == hipSuccess && own_floats)
+        e = ev[1].create();
+    if (e == hipSuccess)
+        e = hipMemset(pcm.get(), 0, pool);
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        return set_err("lamehip_batch_set_sample_type: device allocation", e);
+    }
+    b->d_pcm = std::move(pcm);
+    b->h_pcm.release();         /* (none yet: asking for the mirror hands PCM over) */
+    if (!b->rate_in) {
+        b->d_pcmf = std::move(pcmf);    /* (back to s16: released) */
+        b->capf = own_floats ? b->cap : 0;
+        b->d_in_streams = std::move(streams);
+        b->ev_in[0] = std::move(ev[0]);
+        b->ev_in[1] = std::move(ev[1]);
+    }
+    b->in_dirty.assign((size_t) b->B, 0);
+    b->stype = type;
+    b->esz = esz;
+    return 0;
+}
+
+/* test accessor: the float planes of stream s as the encoder reads them -- the converted signal (after
+ * lamehip_batch_set_pcm when the host converts, after lamehip_batch_encode when the device does), or what the ingest made
+ * of a typed stream (after lamehip_batch_encode); returns the length, or a negative code */
 extern "C" long
 lamehip_batch_get_converted(lamehip_batch * b, int s, float *l, float *r, long cap)
 {
     LhDeviceScope const on_device(b ? b->device : -1);
-    if (!b || s < 0 || s >= b->B || !b->rate_in || !l || !r)
+    if (!b || s < 0 || s >= b->B || !batch_reads_floats(b) || !l || !r)
         return -1;
-    if (b->dev_rs && b->rs_dirty[(size_t) s]) {
+    if (b->dev_rs ? b->rs_dirty[(size_t) s] : (b->stype != LH_PCM_S16 && b->in_dirty[(size_t) s])) {
         snprintf(g_err, sizeof(g_err), "lamehip_batch_get_converted: stream %d has not been converted yet (lamehip_batch_encode)", s);
         return -1;
     }
@@ -1406,6 +1688,13 @@ extern "C" float
 lamehip_batch_last_resample_ms(lamehip_batch * b)
 {
     return b ? b->rs_ms : 0.0f;
+}
+
+/* HIP-event time of the ingest kernel of the last lamehip_batch_encode (after lamehip_batch_sync); 0 when none ran */
+extern "C" float
+lamehip_batch_last_ingest_ms(lamehip_batch * b)
+{
+    return b ? b->in_ms : 0.0f;
 }
 
 /* bytes of one stream as the device packed them (audio frames incl. the final padding, no tag) */
@@ -1551,6 +1840,11 @@ lamehip_batch_sync(lamehip_batch * b)
         if (b->rs_ran && hipEventElapsedTime(&b->rs_ms, b->ev_rs[0], b->ev_rs[1]) != hipSuccess) {
             (void) hipGetLastError();
             b->rs_ms = 0;
+        }
+        b->in_ms = 0;
+        if (b->in_ran && hipEventElapsedTime(&b->in_ms, b->ev_in[0], b->ev_in[1]) != hipSuccess) {
+            (void) hipGetLastError();
+            b->in_ms = 0;
         }
         if (hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess)
             b->last_ms = ms;

@@ -1,6 +1,7 @@
 /*
  * lh_resample_dev.hip -- the rate converter of a batch on the device (gfx950): fills the batch's float pool
- * from its s16 pool, bit for bit what lh_rs_block (lh_resample.c) makes of the same samples.
+ * from its input pool -- s16, or the int32 / float pool of a typed batch (lh_pcm_in.h: the type's norm is part of
+ * the matrix) --, bit for bit what lh_rs_block (lh_resample.c) makes of the same samples.
  *
  * The converter's serial part -- which blocks there are, and the clock each starts at -- is a plan the host
  * makes from the stream lengths alone (lh_rs_plan_tail / lh_rs_trunk_extend).  Given its block an output
@@ -25,7 +26,7 @@
 #define LH_RS_DEVICE
 #define LH_RS_FN static __device__ __forceinline__
 #endif
-#include "lh_rs_sample.h"
+#include "lh_pcm_in.h"
 
 #define LH_RS_NT 256
 
@@ -33,9 +34,9 @@ struct alignas(16) LhRsF4 {
     float   v[4];
 };
 
-template < int TAPS > LH_RS_FN void
+template < int TAPS, typename T > LH_RS_FN void
 rs_convert_block(const LhRsParams & p, const float *bank, const LhRsBlock & blk, long long n,
-                 const int16_t * in_l, const int16_t * in_r, float *out_l, float *out_r, float (*xs)[LH_RS_SPAN_MAX])
+                 const T * in_l, const T * in_r, float *out_l, float *out_r, float (*xs)[LH_RS_SPAN_MAX])
 {
     int const tid = (int) threadIdx.x;
     if (blk.made <= 0)
@@ -82,14 +83,14 @@ rs_convert_block(const LhRsParams & p, const float *bank, const LhRsBlock & blk,
 }
 
 /* grid: x = block of the stream, y = entry of `streams' */
-template < int TAPS >
+template < int TAPS, typename T >
 #ifndef LH_EMU
 __global__ void __launch_bounds__(LH_RS_NT)
 #else
 void
 #endif
 lh_resample_kernel(LhRsParams p, const float *bank, const LhRsBlock * trunk, const LhRsBlock * tails, const LhRsStream * streams,
-                   const int16_t * pcm, float *pcmf)
+                   const T * pcm, float *pcmf)
 {
     __shared__ float xs[2][LH_RS_SPAN_MAX];
     LhRsStream const sd = streams[blockIdx.y];
@@ -97,16 +98,15 @@ lh_resample_kernel(LhRsParams p, const float *bank, const LhRsBlock * trunk, con
     if (j >= sd.ntrunk + sd.ntail)
         return;
     LhRsBlock const blk = j < sd.ntrunk ? trunk[j] : tails[sd.tail_at + (j - sd.ntrunk)];
-    const int16_t *in_l = pcm + (size_t) sd.stream * 2 * (size_t) p.cap_in, *in_r = in_l + p.cap_in;
+    const T *in_l = pcm + (size_t) sd.stream * 2 * (size_t) p.cap_in, *in_r = in_l + p.cap_in;
     float  *out_l = pcmf + (size_t) sd.stream * 2 * (size_t) p.cap_out, *out_r = out_l + p.cap_out;
-    rs_convert_block < TAPS > (p, bank, blk, sd.n, in_l, in_r, out_l, out_r, xs);
+    rs_convert_block < TAPS, T > (p, bank, blk, sd.n, in_l, in_r, out_l, out_r, xs);
 }
 
 #ifndef LH_EMU
-/* nstreams entries of `streams', the longest with max_blocks blocks.  Returns a hipError_t. */
-extern "C" int
-lh_launch_resample(const LhRsParams * p, const float *bank, const LhRsBlock * trunk, const LhRsBlock * tails,
-                   const LhRsStream * streams, int nstreams, int max_blocks, const int16_t * pcm, float *pcmf, void *stream)
+template < typename T > static int
+rs_launch(const LhRsParams * p, const float *bank, const LhRsBlock * trunk, const LhRsBlock * tails, const LhRsStream * streams,
+          int nstreams, int max_blocks, const T * pcm, float *pcmf, void *stream)
 {
     if (nstreams <= 0 || max_blocks <= 0)
         return 0;
@@ -117,10 +117,10 @@ lh_launch_resample(const LhRsParams * p, const float *bank, const LhRsBlock * tr
         int const ns = nstreams - at < 65535 ? nstreams - at : 65535;
         dim3 const grid((unsigned) max_blocks, (unsigned) ns), block(LH_RS_NT);
         if (p->taps == 31)
-            hipLaunchKernelGGL((lh_resample_kernel < 31 >), grid, block, 0, (hipStream_t) stream, *p, bank, trunk, tails, streams + at,
+            hipLaunchKernelGGL((lh_resample_kernel < 31, T >), grid, block, 0, (hipStream_t) stream, *p, bank, trunk, tails, streams + at,
                                pcm, pcmf);
         else
-            hipLaunchKernelGGL((lh_resample_kernel < 32 >), grid, block, 0, (hipStream_t) stream, *p, bank, trunk, tails, streams + at,
+            hipLaunchKernelGGL((lh_resample_kernel < 32, T >), grid, block, 0, (hipStream_t) stream, *p, bank, trunk, tails, streams + at,
                                pcm, pcmf);
         hipError_t const e = hipGetLastError();
         if (e != hipSuccess)
@@ -128,10 +128,36 @@ lh_launch_resample(const LhRsParams * p, const float *bank, const LhRsBlock * tr
     }
     return 0;
 }
-#else
+
+/* nstreams entries of `streams', the longest with max_blocks blocks; `pcm' is a pool of `type' (LH_PCM_*), whose norm
+ * the caller has put into p->m (lh_pcm_matrix).  Returns a hipError_t. */
 extern "C" int
-lh_emu_resample(const LhRsParams * params, const float *bank, const LhRsBlock * trunk, const LhRsBlock * tails,
-                const LhRsStream * streams, int nstreams, int max_blocks, const int16_t * pcm, float *pcmf)
+lh_launch_resample_typed(int type, const LhRsParams * p, const float *bank, const LhRsBlock * trunk, const LhRsBlock * tails,
+                         const LhRsStream * streams, int nstreams, int max_blocks, const void *pcm, float *pcmf, void *stream)
+{
+    switch (type) {
+    case LH_PCM_S16:
+        return rs_launch(p, bank, trunk, tails, streams, nstreams, max_blocks, (const int16_t *) pcm, pcmf, stream);
+    case LH_PCM_S32:
+        return rs_launch(p, bank, trunk, tails, streams, nstreams, max_blocks, (const int32_t *) pcm, pcmf, stream);
+    case LH_PCM_F32:
+    case LH_PCM_F32_UNIT:
+        return rs_launch(p, bank, trunk, tails, streams, nstreams, max_blocks, (const float *) pcm, pcmf, stream);
+    }
+    return (int) hipErrorInvalidValue;
+}
+
+/* the s16 case */
+extern "C" int
+lh_launch_resample(const LhRsParams * p, const float *bank, const LhRsBlock * trunk, const LhRsBlock * tails,
+                   const LhRsStream * streams, int nstreams, int max_blocks, const int16_t * pcm, float *pcmf, void *stream)
+{
+    return rs_launch(p, bank, trunk, tails, streams, nstreams, max_blocks, pcm, pcmf, stream);
+}
+#else
+template < typename T > static int
+rs_emu(const LhRsParams * params, const float *bank, const LhRsBlock * trunk, const LhRsBlock * tails, const LhRsStream * streams,
+       int nstreams, int max_blocks, const T * pcm, float *pcmf)
 {
     LhRsParams const p = *params;
     hipemu_dim3 grid = { (unsigned) max_blocks, (unsigned) nstreams, 1 }, block = { LH_RS_NT, 1, 1 };
@@ -139,11 +165,34 @@ lh_emu_resample(const LhRsParams * params, const float *bank, const LhRsBlock * 
         return 0;
     hipemu_run(grid, block,[=] () {
                if (p.taps == 31)
-                   lh_resample_kernel < 31 > (p, bank, trunk, tails, streams, pcm, pcmf);
+                   lh_resample_kernel < 31, T > (p, bank, trunk, tails, streams, pcm, pcmf);
                else
-                   lh_resample_kernel < 32 > (p, bank, trunk, tails, streams, pcm, pcmf);
+                   lh_resample_kernel < 32, T > (p, bank, trunk, tails, streams, pcm, pcmf);
                }
     );
     return 0;
+}
+
+extern "C" int
+lh_emu_resample_typed(int type, const LhRsParams * params, const float *bank, const LhRsBlock * trunk, const LhRsBlock * tails,
+                      const LhRsStream * streams, int nstreams, int max_blocks, const void *pcm, float *pcmf)
+{
+    switch (type) {
+    case LH_PCM_S16:
+        return rs_emu(params, bank, trunk, tails, streams, nstreams, max_blocks, (const int16_t *) pcm, pcmf);
+    case LH_PCM_S32:
+        return rs_emu(params, bank, trunk, tails, streams, nstreams, max_blocks, (const int32_t *) pcm, pcmf);
+    case LH_PCM_F32:
+    case LH_PCM_F32_UNIT:
+        return rs_emu(params, bank, trunk, tails, streams, nstreams, max_blocks, (const float *) pcm, pcmf);
+    }
+    return -1;
+}
+
+extern "C" int
+lh_emu_resample(const LhRsParams * params, const float *bank, const LhRsBlock * trunk, const LhRsBlock * tails,
+                const LhRsStream * streams, int nstreams, int max_blocks, const int16_t * pcm, float *pcmf)
+{
+    return rs_emu(params, bank, trunk, tails, streams, nstreams, max_blocks, pcm, pcmf);
 }
 #endif

@@ -17,6 +17,10 @@ LIB_PATH = os.environ.get("LAMEHIP_LIB", os.path.join(_HERE, "liblamehip.so"))  
 
 ERR_NODEVICE = -10
 STEREO, JOINT_STEREO = 0, 1
+# sample types of a batch (LAMEHIP_PCM_* in include/lamehip.h) and the element each is made of
+PCM_S16, PCM_S32, PCM_F32, PCM_F32_UNIT = 0, 1, 2, 3
+PCM_DTYPES = {PCM_S16: np.dtype(np.int16), PCM_S32: np.dtype(np.int32), PCM_F32: np.dtype(np.float32),
+              PCM_F32_UNIT: np.dtype(np.float32)}
 
 _lib = None
 
@@ -72,12 +76,39 @@ def load_library():
     lib.lamehip_batch_kernel_waves.argtypes = [C.c_void_p]
     lib.lamehip_batch_last_windows.restype = C.c_int
     lib.lamehip_batch_last_windows.argtypes = [C.c_void_p]
+    lib.lamehip_batch_set_sample_type.argtypes = [C.c_void_p, C.c_int]
+    lib.lamehip_batch_set_input.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_long]
+    lib.lamehip_batch_set_input_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_long]
+    lib.lamehip_batch_input_host_ptr.restype = C.c_void_p
+    lib.lamehip_batch_input_host_ptr.argtypes = [C.c_void_p]
+    lib.lamehip_batch_last_ingest_ms.restype = C.c_float
+    lib.lamehip_batch_last_ingest_ms.argtypes = [C.c_void_p]
     _lib = lib
     return lib
 
 
 def last_error():
     return load_library().lamehip_last_error().decode()
+
+
+def _is_device_array(x):
+    """a torch tensor on a GPU, or anything else that says where its samples live the same way (torch is never imported)"""
+    return hasattr(x, "data_ptr") and bool(getattr(x, "is_cuda", False))
+
+
+def _check_input(x, dtype, what):
+    """x as the batch's set_input takes it -- a numpy array, or a device array, of exactly `dtype', C-contiguous: never cast"""
+    if _is_device_array(x):
+        name = str(x.dtype).split(".")[-1]
+        if name != dtype.name:
+            raise TypeError("set_input: %s is %s, the batch's sample type takes %s" % (what, name, dtype.name))
+        if not x.is_contiguous():
+            raise ValueError("set_input: %s is not contiguous" % what)
+        return x
+    x = np.asarray(x)
+    if x.dtype != dtype:
+        raise TypeError("set_input: %s is %s, the batch's sample type takes %s" % (what, x.dtype.name, dtype.name))
+    return np.ascontiguousarray(x)
 
 
 class Encoder:
@@ -178,6 +209,60 @@ class Batch:
             self.b = C.c_void_p(self.lib.lamehip_batch_create_on(int(device), enc.h, nstreams, capacity))
         if not self.b:
             raise RuntimeError("lamehip_batch_create failed: %s" % last_error())
+        self.sample_type = PCM_S16
+
+    def set_sample_type(self, t):
+        """The element type of the batch's input (PCM_S16 / PCM_S32 / PCM_F32 / PCM_F32_UNIT: int16, int32 at +/- 2^31,
+        float32 at +/- 32768, float32 at +/- 1.0).  Before any PCM is handed over; other than PCM_S16, encode() turns the
+        input pool into the floats the kernels read with a kernel of its own (ingest_ms())."""
+        rc = self.lib.lamehip_batch_set_sample_type(self.b, int(t))
+        if rc:
+            raise RuntimeError("lamehip_batch_set_sample_type failed (%d): %s" % (rc, last_error()))
+        self.sample_type = int(t)
+
+    def set_input(self, s, left=None, right=None, interleaved=None):
+        """Stream s's samples in the batch's sample type: planar `left' / `right' (right=None: mono), or one interleaved
+        array [n, 2] (as `interleaved', or as a two-dimensional `left').  numpy arrays go through the pinned mirror; arrays
+        that live on the batch's GPU (anything with data_ptr() and is_cuda, such as a torch tensor) are copied on the
+        device -- whatever produced them must have finished.  The dtype must be the batch's: nothing is cast."""
+        dtype = PCM_DTYPES[self.sample_type]
+        if interleaved is None and left is not None and right is None and len(getattr(left, "shape", ())) == 2:
+            interleaved, left = left, None
+        if interleaved is not None:
+            if left is not None or right is not None:
+                raise ValueError("set_input: planar arrays or an interleaved one, not both")
+            x = _check_input(interleaved, dtype, "interleaved")
+            if len(x.shape) != 2 or x.shape[1] != 2:
+                raise ValueError("set_input: an interleaved array is [n, 2]")
+            n, stride = int(x.shape[0]), 2
+            base = x.data_ptr() if _is_device_array(x) else x.ctypes.data
+            ptrs, keep = (base, base + dtype.itemsize), (x,)
+        else:
+            l = _check_input(left, dtype, "left")
+            r = l if right is None else _check_input(right, dtype, "right")     # mono: not read
+            if len(l.shape) != 1 or tuple(r.shape) != tuple(l.shape) or _is_device_array(l) != _is_device_array(r):
+                raise ValueError("set_input: planar input is two one-dimensional arrays of one length, in one place")
+            n, stride = int(l.shape[0]), 1
+            ptrs = (l.data_ptr(), r.data_ptr()) if _is_device_array(l) else (l.ctypes.data, r.ctypes.data)
+            keep = (l, r)
+        fn = self.lib.lamehip_batch_set_input_device if _is_device_array(keep[0]) else self.lib.lamehip_batch_set_input
+        rc = fn(self.b, s, ptrs[0], ptrs[1], stride, n)
+        if rc:
+            raise RuntimeError("lamehip_batch_set_input failed (%d): %s" % (rc, last_error()))
+
+    def input_host(self):
+        """The pinned host mirror of the input pool in the batch's sample type, [streams, 2, capacity] (no copy): fill it,
+        then set_length(s, n) + mark_pcm(s), as with pcm_host()."""
+        p = self.lib.lamehip_batch_input_host_ptr(self.b)
+        if not p:
+            raise RuntimeError("no pinned mirror for this batch: %s" % last_error())
+        dtype = PCM_DTYPES[self.sample_type]
+        buf = (C.c_char * (self.n * 2 * self.capacity * dtype.itemsize)).from_address(p)
+        return np.frombuffer(buf, dtype=dtype).reshape(self.n, 2, self.capacity)
+
+    def ingest_ms(self):
+        """HIP-event time of the last encode()'s ingest kernel (input pool -> float pool), 0 when none ran."""
+        return float(self.lib.lamehip_batch_last_ingest_ms(self.b))
 
     def set_pcm(self, s, left, right=None):
         left = np.ascontiguousarray(left, dtype=np.int16)

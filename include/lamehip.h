@@ -234,8 +234,9 @@ void    lamehip_batch_destroy(lamehip_batch *);
 int     lamehip_batch_set_pcm(lamehip_batch *, int stream, const short *l, const short *r, long nsamples);
 /* same, from planar s16 buffers that already live in HBM (D2D) */
 int     lamehip_batch_set_pcm_device(lamehip_batch *, int stream, const void *dev_l, const void *dev_r, long nsamples);
-/* device pointer of the PCM pool: int16 [stream][2][capacity]; lets a producer
- * that already lives on the GPU fill it in place (then declare lengths) */
+/* device pointer of the PCM pool: int16 [stream][2][capacity] -- int32 or float on a batch of another sample type
+ * (lamehip_batch_set_sample_type) --; lets a producer that already lives on the GPU fill it in place (then declare
+ * lengths) */
 void   *lamehip_batch_pcm_device_ptr(lamehip_batch *);
 int     lamehip_batch_set_length(lamehip_batch *, int stream, long nsamples);
 /* Rate conversion on the device, for a batch whose input rate differs from its output rate (-1 for any other, and
@@ -251,12 +252,46 @@ int     lamehip_batch_set_length(lamehip_batch *, int stream, long nsamples);
  * batch either way. */
 int     lamehip_batch_set_device_resampling(lamehip_batch *, int on);
 /* test accessor: the converted signal of a stream (float planes as the encoder reads them), valid after
- * lamehip_batch_set_pcm when the host converts and after lamehip_batch_encode when the device does; waits for the
+ * lamehip_batch_set_pcm when the host converts and after lamehip_batch_encode when the device does -- also the float
+ * planes of a batch of another sample type that does not convert, after lamehip_batch_encode --; waits for the
  * batch's stream.  Returns the converted length, or a negative code (-1 also when it exceeds cap). */
 long    lamehip_batch_get_converted(lamehip_batch *, int stream, float *l, float *r, long cap);
 /* HIP-event time in ms of the device conversion of the last lamehip_batch_encode (after lamehip_batch_sync); 0 when
  * none ran.  It is not part of lamehip_batch_last_kernel_ms / _parts_ms. */
 float   lamehip_batch_last_resample_ms(lamehip_batch *);
+
+/* Sample types of a batch's input, each named after the reference entry point whose bytes it reproduces (lame.c:1786-1972:
+ * lame_encode_buffer_template with the type's norm, lame_copy_inbuffer's arithmetic in float): */
+#define LAMEHIP_PCM_S16      0  /* int16_t, +/- 32768: lame_encode_buffer (the default) */
+#define LAMEHIP_PCM_S32      1  /* int32_t, +/- 2^31:  lame_encode_buffer_int */
+#define LAMEHIP_PCM_F32      2  /* float,   +/- 32768: lame_encode_buffer_float */
+#define LAMEHIP_PCM_F32_UNIT 3  /* float,   +/- 1.0:   lame_encode_buffer_ieee_float */
+/* The batch's sample type.  Only before any PCM, length or mirror has been handed over (-1 after, and lamehip_last_error()
+ * says so).  With a type other than s16 the batch holds an input pool T [stream][2][capacity] of that element type (pinned
+ * mirror, device pointer, lamehip_batch_set_length, _mark_pcm and _upload work on it as on the s16 pool) and a float pool
+ * [stream][2][capacity] that the kernels read: 8 bytes per sample and plane in HBM against 2.  lamehip_batch_encode fills
+ * the float pool from the input pool with a kernel on the batch's stream, in front of the analysis kernels, for the streams
+ * declared (lamehip_batch_set_input* / _set_length / _mark_pcm) since their last ingest; samples at or beyond a stream's
+ * length are never read.  Same floats as the reference's lame_copy_inbuffer, hence the bytes of the entry point named above.
+ * On a batch whose input rate differs from its output rate a type other than s16 needs
+ * lamehip_batch_set_device_resampling(b, 1) first (-1 otherwise: the host converter takes s16 only); the converter then
+ * reads the typed pool itself.  An allocation failure returns LAMEHIP_ERR_DEVICE and leaves the batch as it was.
+ * lamehip_batch_append, lamehip_batch_set_pcm and lamehip_batch_set_pcm_device (the calls that take shorts) are refused on a
+ * batch of another type, and lamehip_batch_pcm_host_ptr returns NULL. */
+int     lamehip_batch_set_sample_type(lamehip_batch *, int type);
+/* one stream's samples, of the batch's element type, from host buffers: l and r advance by `stride' elements per sample --
+ * 1: planar; 2: interleaved with r = l + 1, as lame_encode_buffer_interleaved* is called.  Through the pinned mirror where
+ * there is one, like lamehip_batch_set_pcm; mono without a downmix reads l only.  Works on an s16 batch too. */
+int     lamehip_batch_set_input(lamehip_batch *, int stream, const void *l, const void *r, int stride, long nsamples);
+/* the same from buffers in HBM, synchronous like lamehip_batch_set_pcm_device: two device-to-device copies for stride 1, a
+ * small kernel that takes the interleaved buffer apart for stride 2.  Whatever produced the buffers must have finished. */
+int     lamehip_batch_set_input_device(lamehip_batch *, int stream, const void *dev_l, const void *dev_r, int stride, long nsamples);
+/* the pinned mirror of the input pool in the batch's element type, [stream][2][capacity] (lamehip_batch_pcm_host_ptr for
+ * any type; the same rules: ask again before rewriting rows an asynchronous upload has taken) */
+void   *lamehip_batch_input_host_ptr(lamehip_batch *);
+/* HIP-event time in ms of the ingest kernel of the last lamehip_batch_encode (after lamehip_batch_sync); 0 when none ran.
+ * Like lamehip_batch_last_resample_ms it is not part of lamehip_batch_last_kernel_ms / _parts_ms. */
+float   lamehip_batch_last_ingest_ms(lamehip_batch *);
 
 /* Incremental use -- lame_encode_buffer (lame.h:715-722, lame.c:1672-1775) for all streams of a batch at once:
  *   lamehip_batch_append            stage n more samples of one stream (host, pinned memory; any n >= 0, ragged
