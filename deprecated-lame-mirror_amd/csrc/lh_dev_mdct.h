@@ -25,8 +25,6 @@
 #define LH_WINV(t,i) LH_MDCT_WIN[(t)*36+(i)]
 #define LH_TANTAB(i) LH_WIN(LH_SHORT_TYPE, 3 + (i))
 #define LH_CX(i) LH_WIN(LH_SHORT_TYPE, 12 + (i))
-#define LH_CA(i) LH_WIN(LH_SHORT_TYPE, 20 + (i))
-#define LH_CS(i) LH_WIN(LH_SHORT_TYPE, 28 + (i))
 #define LH_WK(n) LH_ENW[287 - 18 * (n)]
 
 #define LH_BX(m,s,c)  do { float xr_ = a[m] - a[s]; a[s] += a[m]; a[m] = xr_ * (c); } while (0)

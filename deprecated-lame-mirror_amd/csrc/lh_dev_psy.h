@@ -60,51 +60,6 @@ lh_ms_thresholds(const LhCtx & c, const float *eb, float *thr, const float *cb_m
     }
 }
 
-/* perceptual entropy of one pseudo-channel (reference psymodel.c:458-553); serial, one lane.
- * en/thm point at a 61-entry III_psy_xmin image (l[22], s[13][3]) */
-LH_DEVFN float
-lh_pecalc(const LhTables * T, const float *en, const float *thm, float masking_lower, int is_short)
-{
-    float   pe;
-    if (is_short) {
-        pe = 1236.28f / 4;
-        for (int sb = 0; sb < LH_SBMAX_S - 1; sb++) {
-            for (int sblock = 0; sblock < 3; sblock++) {
-                float const t = thm[22 + sb * 3 + sblock];
-                if (t > 0.0f) {
-                    float const x = t * masking_lower;
-                    float const e = en[22 + sb * 3 + sblock];
-                    if (e > x) {
-                        if (e > x * 1e10f)
-                            pe = (float) (pe + lh_regcoef_s[sb] * (10.0f * 2.30258509299404568402));
-                        else
-                            pe = (float) (pe + lh_regcoef_s[sb] *
-                                          (lh_fast_log2(T->log_table, e / x) * LH_LOG2_OVER_LOG10));
-                    }
-                }
-            }
-        }
-    }
-    else {
-        pe = 1124.23f / 4;
-        for (int sb = 0; sb < LH_SBMAX_L - 1; sb++) {
-            float const t = thm[sb];
-            if (t > 0.0f) {
-                float const x = t * masking_lower;
-                float const e = en[sb];
-                if (e > x) {
-                    if (e > x * 1e10f)
-                        pe = (float) (pe + lh_regcoef_l[sb] * (10.0f * 2.30258509299404568402));
-                    else
-                        pe = (float) (pe + lh_regcoef_l[sb] *
-                                      (lh_fast_log2(T->log_table, e / x) * LH_LOG2_OVER_LOG10));
-                }
-            }
-        }
-    }
-    return pe;
-}
-
 #ifdef LH_SPLIT
 /* The encode kernel of the split pipeline (lh_kernels.hip with -DLH_SPLIT): the analysis kernels (lh_analysis.hip) have
  * done everything of a granule's masking that depends on the PCM alone -- lh_compute_masking < NC, 1 > left the partition

@@ -322,7 +322,7 @@ lq_quantize(const LhCtx & c, LhQS & S, const LhQR & R, const LhGrR & g)
      * (LhTables.qthr; both in tests/test_quantizer_identity.py) ---- */
     {
         uint32_t nq[5];
-#if !defined(LH_EMU) && !defined(LH_NO_JOIN)
+#if !defined(LH_EMU)
         /* all of the threshold look-ups behind ONE s_waitcnt (the compiler's own would be one per comparison: eight issue
          * slots of a wave that has none to spare; the look-ups went out before the band masks were formed) */
         if (NS == 4)
@@ -337,7 +337,7 @@ lq_quantize(const LhCtx & c, LhQS & S, const LhQR & R, const LhGrR & g)
             uint32_t const b0 = qb[2 * k], b1 = qb[2 * k + 1];
             float const t0 = qt_[2 * k], t1 = qt_[2 * k + 1];
             uint32_t const r0 = b0 - (a0 < t0 ? 1u : 0u), r1 = b1 - (a1 < t1 ? 1u : 0u);
-#if !defined(LH_EMU) && !defined(LH_NO_BFE_SELECT)
+#if !defined(LH_EMU)
             /* (the two low halves into one word: one v_perm_b32 instead of v_and + v_lshl_or; masked where it is used) */
             nq[k] = __builtin_amdgcn_perm(r1, r0, 0x05040100u);
 #else
@@ -353,7 +353,7 @@ lq_quantize(const LhCtx & c, LhQS & S, const LhQR & R, const LhGrR & g)
                 nq[k] = ((uint32_t) (q0 & 0xffff) | ((uint32_t) q1 << 16)) & S.vm[k];
             }
         }
-#if !defined(LH_EMU) && !defined(LH_NO_BFE_SELECT)
+#if !defined(LH_EMU)
         /* (with the previous call's data in play, a long-block granule takes the selecting path below every time: "all bands
          * anew, none by the 0 / 1 comparator" is one more pair of masks to it, not a branch of its own) */
         int const merged = USE_PREV && R.block_type != LH_SHORT_TYPE;
@@ -369,7 +369,7 @@ lq_quantize(const LhCtx & c, LhQS & S, const LhQR & R, const LhGrR & g)
             /* (1 - 0.4054) / istep: istep is one of 16 mantissas times a power of two, and a correctly rounded quotient
              * scales exactly -- the 16 quotients sit in lanes 32..47 of S.istepv */
             float const compareval0 = cmpv;
-#if !defined(LH_EMU) && !defined(LH_NO_BFE_SELECT)
+#if !defined(LH_EMU)
             /* long-block granules have 22 bands: the two band masks fit a word each, a signed one-bit field extract at the
              * lane's band (v_bfe_i32) is 0 or ~0 for the whole word, and two v_bfi_b32 take the place of the two selects --
              * four instructions per slot instead of eight (two 64-bit bit tests of three instructions each + the selects) */
@@ -677,24 +677,15 @@ lq_count(const LhCtx & c, LhQS & S, LhQR & R, LhGrR & g, LhChanLds & Q)
     }
 }
 
-template < int NS > LH_DEVFN void lq_noise_squares(const LhCtx & c, const LhQS & S, const LhGrR & g, LhChanLds & Q, const float *xr);
-
 /* reference takehiro.c:768-801, count_bits */
 template < int USE_PREV, int NS > LH_DEVFN int
-lq_count_bits(const LhCtx & c, LhQS & S, LhQR & R, LhGrR & g, LhChanLds & Q, const float *xr = nullptr)
+lq_count_bits(const LhCtx & c, LhQS & S, LhQR & R, LhGrR & g, LhChanLds & Q)
 {
     int     bits = LH_LARGE_BITS;
     LH_PC(10);
     LH_PT(t_cb);
-    if (lq_quantize < USE_PREV, NS > (c, S, R, g)) {
-#if defined(LH_NOISE_EARLY) && !defined(LH_EMU)
-        /* (experiment of round 6, DESIGN.md section 4: calc_noise's first half beside the count's reductions and look-ups,
-         * in one instruction stream; wasted when the candidate does not fit and the gain rises) */
-        if (USE_PREV)
-            lq_noise_squares < NS > (c, S, g, Q, xr);
-#endif
+    if (lq_quantize < USE_PREV, NS > (c, S, R, g))
         bits = lq_count < USE_PREV, NS > (c, S, R, g, Q);
-    }
     LH_PA(11, t_cb);
     return bits;
 }
@@ -797,13 +788,13 @@ LH_DEVFN float
 lq_band_sums_pad(const float *sq, int base, int n, int maxw)
 {
     float   noise = 0;
-#if !defined(LH_EMU) && !defined(LH_SUMS_C)
+    (void) maxw;                /* (the callers have it for lq_band_sums; neither walk below needs it) */
+#if !defined(LH_EMU)
     /* One instruction stream for the whole walk: blocks of sixteen terms (four 16-byte reads) in two register sets, the next
      * block's reads in flight under this block's additions; EXEC only ever narrows -- a lane leaves when its band's terms
      * are through (checked per octet: the zero padding runs up to a multiple of eight) and the loop ends with the last lane,
      * so neither the wave's largest width nor a scalar loop count is needed; EXEC comes back at the end, behind a wait for
      * the reads still in flight (the temporaries are plain clobbers, all of them registers a callee need not preserve: v[192:199], v[208:215], v[224:231], v[240:247] -- the others of that range would be saved to scratch at the stage's entry, 4 KB per call that the L2 writes back to HBM). */
-    (void) maxw;
     int     rem = n;            /* terms the lane still has to add (<= 0: none) */
     uint32_t ad = lh_lds_off(sq) + 4u * (uint32_t) base;
     unsigned long long sv_, tm_;
@@ -850,41 +841,7 @@ lq_band_sums_pad(const float *sq, int base, int n, int maxw)
                    "v212", "v213", "v214", "v215", "v224", "v225", "v226", "v227", "v228", "v229", "v230", "v231",
                    "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247");
 #undef LQ_OCT
-#elif !defined(LH_EMU)
-    struct alignas(16) Q4 { float x, y, z, w; };
-    const Q4 *src = (const Q4 *) (sq + base);
-    int     rem = n;            /* terms the lane still has to add (<= 0: none) */
-    Q4      a0 = src[0], a1 = src[1], a2 = src[2], a3 = src[3];
-#define LH_CP_OCT(K, A, B) "v_cmpx_gt_i32_e64 %[tm], %[rem], " #K "\n\t" \
-                           "v_add_f32 %[ns], %[ns], %[" #A "0]\n\tv_add_f32 %[ns], %[ns], %[" #A "1]\n\t" \
-                           "v_add_f32 %[ns], %[ns], %[" #A "2]\n\tv_add_f32 %[ns], %[ns], %[" #A "3]\n\t" \
-                           "v_add_f32 %[ns], %[ns], %[" #B "0]\n\tv_add_f32 %[ns], %[ns], %[" #B "1]\n\t" \
-                           "v_add_f32 %[ns], %[ns], %[" #B "2]\n\tv_add_f32 %[ns], %[ns], %[" #B "3]\n\t"
-#define LH_CP_BLOCK(U, V, W, X) do { unsigned long long sv_, tm_; \
-                asm volatile("s_mov_b64 %[sv], exec\n\t" LH_CP_OCT(0, a, b) LH_CP_OCT(8, c, d) "s_mov_b64 exec, %[sv]" \
-                             : [ns] "+v"(noise), [sv] "=&s"(sv_), [tm] "=&s"(tm_) \
-                             : [rem] "v"(rem), [a0] "v"(U.x), [a1] "v"(U.y), [a2] "v"(U.z), [a3] "v"(U.w), \
-                               [b0] "v"(V.x), [b1] "v"(V.y), [b2] "v"(V.z), [b3] "v"(V.w), \
-                               [c0] "v"(W.x), [c1] "v"(W.y), [c2] "v"(W.z), [c3] "v"(W.w), \
-                               [d0] "v"(X.x), [d1] "v"(X.y), [d2] "v"(X.z), [d3] "v"(X.w)); } while (0)
-    for (int k0 = 0; k0 < maxw; k0 += 32) {
-        Q4 const b0 = src[4], b1 = src[5], b2 = src[6], b3 = src[7];
-        LH_CP_BLOCK(a0, a1, a2, a3);
-        rem -= 16;
-        if (k0 + 16 >= maxw)
-            break;
-        a0 = src[8];
-        a1 = src[9];
-        a2 = src[10];
-        a3 = src[11];
-        LH_CP_BLOCK(b0, b1, b2, b3);
-        rem -= 16;
-        src += 8;
-    }
-#undef LH_CP_BLOCK
-#undef LH_CP_OCT
 #else
-    (void) maxw;
     for (int i = 0; i < n; i++)
         noise += sq[base + i];
 #endif
@@ -954,7 +911,7 @@ lq_pow20_of_step(const LhQS & S, int st)
 
 /* calc_noise's first half: the squared error of every line of the working image at the working steps, to LDS (sq = the
  * channel's dead xrpow copy), where the band lanes add them up.  A function of the image, the scalefactors and the gain
- * only -- with LH_NOISE_EARLY the bit count that produced the image issues it beside its own reductions and look-ups. */
+ * only. */
 template < int NS > LH_DEVFN void
 lq_noise_squares(const LhCtx & c, const LhQS & S, const LhGrR & g, LhChanLds & Q, const float *xr)
 {
@@ -1002,9 +959,8 @@ lq_noise_squares(const LhCtx & c, const LhQS & S, const LhGrR & g, LhChanLds & Q
     }
 }
 
-/* reference quantize_pvt.c:750-913 on the working image: into `t', S and R stay as they are.  HAVE_SQ: the squared
- * errors are in LDS already (lq_noise_squares ran with the bit count of this very image). */
-template < int NS, int HAVE_SQ = 0 > LH_DEVFN void
+/* reference quantize_pvt.c:750-913 on the working image: into `t', S and R stay as they are. */
+template < int NS > LH_DEVFN void
 lq_calc_noise(const LhCtx & c, const LhQS & S, const LhQR & R, const LhGrR & g, LhChanLds & Q, const float *xr,
               LhNoiseTmp & t)
 {
@@ -1027,8 +983,7 @@ lq_calc_noise(const LhCtx & c, const LhQS & S, const LhQR & R, const LhGrR & g, 
             l = (usefullsize > 0) ? (usefullsize >> 1) : 0;
         }
     }
-    if (!HAVE_SQ)
-        lq_noise_squares < NS > (c, S, g, Q, xr);
+    lq_noise_squares < NS > (c, S, g, Q, xr);
     /* a band that starts at or above the end of the non-zero lines adds up the squares of its own lines, whatever
      * the step: the constant is there since lq_zero_band_noise, and the band sits out the serial sum below (the
      * widest bands are at the top of the spectrum, where little is quantised to anything else) */
@@ -1106,7 +1061,7 @@ lq_scale_mask(LhQS & S, uint64_t bands, float factor, int wide = 1)
     for (int k = 0; k < NS; k++) {
         /* (x * 1.0f == x for every float: one select on the factor instead of one per line) */
         float   f;
-#if !defined(LH_EMU) && !defined(LH_NO_BFE_SELECT)
+#if !defined(LH_EMU)
         /* (long blocks, 22 bands: the band's bit spread over a word by v_bfe_i32 picks the factor's or 1.0f's bits -- two
          * instructions instead of the 64-bit test's three and a select, see lq_quantize) */
         if (!wide) {
@@ -1348,11 +1303,11 @@ lq_balance_noise(const LhCtx & c, LhQS & S, LhChanLds & Q, const LhQR & R, LhGrR
 }
 
 /* where the reference calls calc_noise: the noise of the candidate counted last becomes the working image's */
-template < int NS, int HAVE_SQ = 0 > LH_DEVFN void
+template < int NS > LH_DEVFN void
 lq_noise_point(const LhCtx & c, LhQS & S, LhQR & R, const LhGrR & g, LhChanLds & Q, const float *xr, LhNoiseTmp & t,
                LhNoiseRes & res)
 {
-    lq_calc_noise < NS, HAVE_SQ > (c, S, R, g, Q, xr, t);
+    lq_calc_noise < NS > (c, S, R, g, Q, xr, t);
     lq_noise_commit(S, R, g, t);
     res = t.res;
 }
@@ -1496,7 +1451,7 @@ lq_outer_loop(const LhCtx & c, LhQS & S, LhChanLds & Q, LhQR & R, LhGrR & gb, co
 #endif
             for (;;) {
                 pn_before = R.pn_sfb_count1;
-                gw.part2_3_length = lq_count_bits < 1, NS > (c, S, R, gw, Q, xr);
+                gw.part2_3_length = lq_count_bits < 1, NS > (c, S, R, gw, Q);
                 if (!(gw.part2_3_length > huff_bits && gw.global_gain <= maxggain))
                     break;
                 gw.global_gain++;
@@ -1518,7 +1473,7 @@ lq_outer_loop(const LhCtx & c, LhQS & S, LhChanLds & Q, LhQR & R, LhGrR & gb, co
                 int const same = (R.pn_sfb_count1 == pn_before);
                 if (!same || (gw.part2_3_length > best_part2_3_length && gw.global_gain <= maxggain)) {
                     gw.global_gain += same;     /* (the count that was not run said: too many bits) */
-                    while ((gw.part2_3_length = lq_count_bits < 1, NS > (c, S, R, gw, Q, xr)) > best_part2_3_length
+                    while ((gw.part2_3_length = lq_count_bits < 1, NS > (c, S, R, gw, Q)) > best_part2_3_length
                            && gw.global_gain <= maxggain)
                         gw.global_gain++;
                 }
@@ -1528,11 +1483,7 @@ lq_outer_loop(const LhCtx & c, LhQS & S, LhChanLds & Q, LhQR & R, LhGrR & gb, co
             {
                 LH_PT(t_cn);
                 LQ_T(S, 30);            /* the gain loop's exit checks, the recount rule */
-#if defined(LH_NOISE_EARLY) && !defined(LH_EMU)
-                lq_noise_point < NS, 1 > (c, S, R, gw, Q, xr, nt, noise_info);
-#else
                 lq_noise_point < NS > (c, S, R, gw, Q, xr, nt, noise_info);
-#endif
                 LH_PA(9, t_cn);
             }
             noise_info.bits = gw.part2_3_length;
@@ -1604,11 +1555,7 @@ lq_stage_body(int qch, int gr, int targ_bits)
     }
     LhChanLds & Q = lh_lds.u.quant.ch[qch];
     LhQS    S;
-#if defined(LH_NOISE_EARLY) || defined(LH_NO_PAD)
-    S.pad = 0;
-#else
     S.pad = (SPEC != 0 && !SHORT);
-#endif
     R.s_mnc = lh_uni_i((int) Q.sfb_of_line[R.mnc]);
 #if defined(LH_TRACE) && !defined(LH_EMU)
     lh_tr_begin(S.tr);

@@ -238,107 +238,6 @@ lh_choose_table_wave(const LhCtx & c, const int v[5][2], int lo, int hi, int *bi
     }
 }
 
-/* the same selection done serially by ONE lane over ix[lo,hi) in LDS; used where
- * many independent regions are evaluated at once, one per lane (best_huffman_divide) */
-LH_DEVFN int
-lh_choose_table_lane(const LhQTabs * qt, const int16_t * ix, int lo, int hi, int *bits)
-{
-    unsigned mx = 0;
-    for (int i = lo; i < hi; i++) {
-        unsigned const x = (unsigned) ix[i];
-        mx = x > mx ? x : mx;
-    }
-    if (mx == 0)
-        return 0;
-    if (mx <= 15) {
-        if (mx == 1) {
-            unsigned s = 0;
-            const uint8_t *h1 = LH_HLEN(1);
-            for (int i = lo; i < hi; i += 2)
-                s += h1[ix[i] + ix[i] + ix[i + 1]];
-            *bits += (int) s;
-            return 1;
-        }
-        if (mx <= 3) {
-            int     t1 = lh_huf_noESC(mx);
-            unsigned const xlen = lh_ht_xlen_c(t1);
-            const uint32_t *table = (t1 == 2) ? qt->table23 : qt->table56;
-            unsigned s = 0, s2;
-            for (int i = lo; i < hi; i += 2)
-                s += table[(unsigned) ix[i] * xlen + (unsigned) ix[i + 1]];
-            s2 = s & 0xffffu;
-            s >>= 16u;
-            if (s > s2) {
-                s = s2;
-                t1++;
-            }
-            *bits += (int) s;
-            return t1;
-        }
-        {
-            int const t1 = lh_huf_noESC(mx);
-            unsigned const xlen = lh_ht_xlen_c(t1);
-            const uint8_t *h1 = LH_HLEN(t1), *h2 = LH_HLEN(t1 + 1), *h3 = LH_HLEN(t1 + 2);
-            unsigned s1 = 0, s2 = 0, s3 = 0;
-            int     t;
-            for (int i = lo; i < hi; i += 2) {
-                unsigned const x = (unsigned) ix[i] * xlen + (unsigned) ix[i + 1];
-                s1 += h1[x];
-                s2 += h2[x];
-                s3 += h3[x];
-            }
-            t = t1;
-            if (s1 > s2) {
-                s1 = s2;
-                t++;
-            }
-            if (s1 > s3) {
-                s1 = s3;
-                t = t1 + 2;
-            }
-            *bits += (int) s1;
-            return t;
-        }
-    }
-    if (mx > LH_IXMAX) {
-        *bits = LH_LARGE_BITS;
-        return -1;
-    }
-    {
-        int     choice, choice2;
-        unsigned const m15 = mx - 15u;
-        unsigned sa = 0, sb = 0, n15 = 0;
-        for (choice2 = 24; choice2 < 32; choice2++)
-            if (lh_ht_linmax_c(choice2) >= m15)
-                break;
-        for (choice = choice2 - 8; choice < 24; choice++)
-            if (lh_ht_linmax_c(choice) >= m15)
-                break;
-        for (int i = lo; i < hi; i += 2) {
-            unsigned x = (unsigned) ix[i], y = (unsigned) ix[i + 1], e;
-            if (x >= 15u) {
-                x = 15u;
-                n15++;
-            }
-            if (y >= 15u) {
-                y = 15u;
-                n15++;
-            }
-            e = lh_largetbl[(x << 4) + y];     /* the constant in HBM: not a hot path */
-            sa += e >> 16;
-            sb += e & 0xffffu;
-        }
-        sa += n15 * lh_ht_xlen_c(choice);
-        sb += n15 * lh_ht_xlen_c(choice2);
-        if (sa > sb) {
-            sa = sb;
-            choice = choice2;
-        }
-        *bits += (int) sa;
-        return choice;
-    }
-}
-
 /* Look-up parameters of one region, packed for a per-lane select: the candidate tables are
  * read from the byte pool ht_len at o1/o2/o3 + x * xlen + y, or (ESC classes) from largetbl at
  * x * 16 + y; unused candidates alias the first one (their sums are not read). */

@@ -65,16 +65,6 @@ lh_vbr_range_short(int s)
     return s < 18 ? 15 : (s < 36 ? 7 : 0);
 }
 
-/* pow43[] with its LDS head */
-LH_DEVFN float
-lh_pow43(const LhTables * T, const LhQTabs * qt, int k)
-{
-    float   v = qt->pow43h[k & 255];
-    if (k >= 256)
-        v = T->pow43[k];
-    return v;
-}
-
 /* ---- per-granule geometry of the search --------------------------------------------- */
 struct LhVbrGeo {
     int     nb;                 /* bands the block type has (22 / 39) */

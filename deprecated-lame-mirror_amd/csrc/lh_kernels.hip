@@ -319,15 +319,6 @@ lh_prio_tick(int me, int left)
 /* The frame and the stream loop are inlined into the kernel: out of line they saved and restored ~60 registers per
  * frame through scratch memory, 50 KB of HBM traffic per frame at no gain. */
 
-/* The frame's barriers between stages that hand data on through LDS only (LH_SYNC_FRAME): an LDS-only fence.  A full
- * __syncthreads() also drains the wave's global stores -- the payload of the granule just finished -- which nobody in the
- * workgroup reads. */
-#if defined(LH_BAR_LDS) && !defined(LH_EMU)
-#define LH_SYNC_FRAME() LH_SYNC_WG_LDS()
-#else
-#define LH_SYNC_FRAME() LH_SYNC_WG()
-#endif
-
 /* one frame of one stream; executed by the whole workgroup */
 LH_DEVFN void
 lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry)
@@ -366,19 +357,6 @@ lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry)
         constexpr int NM = (int) ((sizeof(LhMidSmall) + sizeof(LhMidLong)) / 16);      /* 420 */
         static_assert(__builtin_offsetof(LhMidFrame, lng) == sizeof(LhMidSmall) && sizeof(LhMidSmall) % 16 == 0, "small and lng are one run");
         lh_f32x4 v[5], m[4];
-#if !defined(LH_EMU) && defined(LH_MID_PREFETCH)
-        /* (off since round 6: the touched lines did not survive a frame's time in the 4 MB of an XCD's L2 beside 128 streams' scratch
-         * and payload lines and were fetched again -- 12.7 KB of the 31.6 KB the kernel read per frame -- for 0.3 % of its time:
-         * profiles/r06_traffic_ab.txt)  The NEXT frame's record is asked for now, one word per cache line (a load nobody uses: it only brings the
-         * lines into the L2 / the memory-side cache, a frame's time before the batch above is issued for them; the pool has
-         * a margin of records behind the launch's last frame).  Issued first, so it has returned when the loads below have. */
-        uint32_t touched;
-        {
-            int const line = tid < 53 ? tid : (tid < 125 ? tid - 53 : 0);
-            const char *nx = (const char *) (rec + 1) + (tid < 53 ? 0 : __builtin_offsetof(LhMidFrame, xr)) + 128 * line;
-            asm volatile("global_load_dword %0, %1, off" : "=v"(touched) : "v"(nx) : "memory");
-        }
-#endif
 #pragma unroll
         for (int u = 0; u < 5; u++)
             v[u] = sx[(tid + LH_NT * u < 576) ? tid + LH_NT * u : 575];
@@ -393,11 +371,8 @@ lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry)
         for (int u = 0; u < 4; u++)
             if (tid + LH_NT * u < NM)
                 dm[tid + LH_NT * u] = m[u];
-#if !defined(LH_EMU) && defined(LH_MID_PREFETCH)
-        asm volatile("" :: "v"(touched));       /* (its register is the load's until here) */
-#endif
     }
-    LH_SYNC_FRAME();
+    LH_SYNC_WG();
 #else
     if (!lh_lds.ss.primed) {
         lh_stage_window(c, L.mf, c.frame_base - fs);
@@ -461,13 +436,13 @@ lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry)
         loud[0][1] = (cfg->channels == 2) ? L.loudness_sq[0][1] : loud[0][0];
         loud[1][1] = (cfg->channels == 2) ? L.loudness_sq[ngr - 1][1] : loud[1][0];
         lh_adjust_ATH(T, loud, &factor, &limit);
-        LH_SYNC_FRAME();
+        LH_SYNC_WG();
         if (tid == 0) {
             lh_lds.ss.ath_adjust_factor = factor;
             lh_lds.ss.ath_adjust_limit = limit;
         }
     }
-    LH_SYNC_FRAME();
+    LH_SYNC_WG();
 
     LH_PA(25, t_frame);
     /* ---- stage 2: polyphase + MDCT (reference encoder.c:405) ---- */
@@ -532,7 +507,7 @@ lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry)
         for (int gr = 0; gr < ngr; gr++)
             for (int ch = 0; ch < nch; ch++)
                 pe_use[gr][ch] = lh_uni_f(pe_use[gr][ch] * f);
-        LH_SYNC_FRAME();
+        LH_SYNC_WG();
         if (tid < 19)
             lh_lds.ss.pefirbuf[tid] = buf[tid];
     }
@@ -629,7 +604,7 @@ lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry)
         int     max_bits = 0;
         if (!abr)
             max_bits = lh_on_pe(cfg, ResvSize, ResvMax, &substep, pe_use[gr], targ_bits, mean_bits, gr);
-        LH_SYNC_FRAME();
+        LH_SYNC_WG();
         substep = lh_uni_i(substep);
         if (mode_ext == LH_MPG_MD_MS_LR && !abr)
             lh_reduce_side(targ_bits, ms_ener_ratio[gr], mean_bits, max_bits);
@@ -644,7 +619,7 @@ lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry)
             st->dbg_mean_bits = mean_bits;
         }
 #endif
-        LH_SYNC_FRAME();
+        LH_SYNC_WG();
         if (w >= nch) {
             /* no second channel: its payload slot is all zero */
             uint32_t *z = (uint32_t *) &fo->gr[gr][w];
@@ -776,14 +751,14 @@ lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry)
                     *(volatile int *) &L.gr0_done[ch] = stamp;
             }
         }
-        LH_SYNC_FRAME();
+        LH_SYNC_WG();
         LH_PRIO_APPLY(carry.prio_rel, carry.prio_late);
         {
             int const used = lh_uni_i(L.bits_used[0] + L.bits_used[1]);
             ResvSize -= used;
             total_bits += used;
         }
-        LH_SYNC_FRAME();
+        LH_SYNC_WG();
     }
     if (abr) {
         /* the smallest frame that brings the reservoir back to a non-negative size
@@ -857,7 +832,7 @@ lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry)
         lh_emit_frame(fo, drain_pre, drain_post, frame_bits / 8, mdb_header, bitrate_index, padding, mode_ext,
                       c.d.flush && (int) ((c.frame_base + LH_MF_START) / fs) == c.d.frame_end - 1);
     LH_PA(0, t_frame);
-    LH_SYNC_FRAME();
+    LH_SYNC_WG();
 #if defined(LH_PROF) && !defined(LH_EMU)
     if (lane < LH_NPROF)
         st->prof[w][lane] += L.prof[w][lane];
@@ -870,44 +845,37 @@ lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry)
 #endif
 /* (the settings and the tables are never written by a kernel: with noalias the loads of their fields move out of the frame loop
  * and across the payload stores: +1 %) */
-#if !defined(LH_EMU) && !defined(LH_NO_RESTRICT)
+#ifndef LH_EMU
 #define LH_RESTRICT __restrict__
 #else
 #define LH_RESTRICT
 #endif
-/* the LH_LSF build of this file (MPEG-2 / 2.5 streams) is a second object in the same library: its own names */
-#if defined(LH_LSF) && !defined(LH_SPLIT)
-#define lh_encode_kernel lh_encode_kernel_lsf
-#define lh_launch_encode lh_launch_encode_lsf
-#define lh_emu_encode lh_emu_encode_lsf
-#define lh_emu_encode_bytes lh_emu_encode_bytes_lsf
-#endif
-/* and so is the LH_VBRK build: the same MPEG-1 source compiled with the scheduling strategy that suits the new VBR
- * loop (csrc/Makefile); lh_api.cpp launches it for vbr_mt / vbr_mtrh configurations */
-#if defined(LH_VBRK) && !defined(LH_SPLIT)
-#define lh_encode_kernel lh_encode_kernel_vbr
-#define lh_launch_encode lh_launch_encode_vbr
-#endif
-/* and the LH_SPLIT builds of all three: the encode kernel of the split pipeline, which starts from the analysis kernels'
- * output (LhMidPools) instead of the PCM */
+/* Every build of this file is one more object in the same library, with names of its own: _q for the LH_SPLIT builds (the
+ * encode kernel of the split pipeline, which starts from the analysis kernels' output, LhMidPools, instead of the PCM), then
+ * _lsf for LH_LSF (MPEG-2 / 2.5 streams) or _vbr for LH_VBRK (the MPEG-1 source compiled with the scheduling strategy that
+ * suits the new VBR loop, csrc/Makefile; lh_api.cpp launches it for vbr_mt / vbr_mtrh configurations). */
 #ifdef LH_SPLIT
-#if defined(LH_LSF)
-#define lh_encode_kernel lh_encode_kernel_q_lsf
-#define lh_launch_encode lh_launch_encode_q_lsf
-#define lh_emu_encode_q lh_emu_encode_q_lsf
-#elif defined(LH_VBRK)
-#define lh_encode_kernel lh_encode_kernel_q_vbr
-#define lh_launch_encode lh_launch_encode_q_vbr
-#else
-#define lh_encode_kernel lh_encode_kernel_q
-#define lh_launch_encode lh_launch_encode_q
-#endif
+#define LH_NAME_Q(n) n##_q
 #define LH_MID_PARAM , LhMidPools mid
 #define LH_MID_ARG , mid
 #else
+#define LH_NAME_Q(n) n
 #define LH_MID_PARAM
 #define LH_MID_ARG
 #endif
+#if defined(LH_LSF)
+#define LH_NAME_G(n) n##_lsf
+#elif defined(LH_VBRK)
+#define LH_NAME_G(n) n##_vbr
+#else
+#define LH_NAME_G(n) n
+#endif
+#define LH_NAME_(n) LH_NAME_G(n)
+#define LH_NAME(n) LH_NAME_(LH_NAME_Q(n))
+#define lh_encode_kernel LH_NAME(lh_encode_kernel)
+#define lh_launch_encode LH_NAME(lh_launch_encode)
+#define lh_emu_encode LH_NAME(lh_emu_encode)    /* (lh_emu_encode_q, lh_emu_encode_q_lsf: the split pipeline's) */
+#define lh_emu_encode_bytes LH_NAME(lh_emu_encode_bytes)
 /* all frames of one stream (the workgroup's whole job) */
 LH_DEVFN void
 lh_encode_stream(const LhConfig * LH_RESTRICT cfg, const LhTables * LH_RESTRICT T, const int16_t * pcm, const float *pcmf,
@@ -1250,9 +1218,9 @@ lh_launch_encode(const LhConfig * cfg, const LhTables * T, const int16_t * pcm, 
 #elif defined(LH_SPLIT)
 /* (emulator, split pipeline: the encode kernel alone; tests/test_emulator.py runs the analysis kernels' twins first) */
 extern "C" int
-lh_emu_encode_q(const LhConfig * cfg, const LhTables * T, const int16_t * pcm, const float *pcmf,
-                const LhStreamDesc * descs, LhStreamState * states, LhFrameOut * out, uint8_t * bytes, int nstreams,
-                const LhMidPools * pools)
+lh_emu_encode(const LhConfig * cfg, const LhTables * T, const int16_t * pcm, const float *pcmf,
+              const LhStreamDesc * descs, LhStreamState * states, LhFrameOut * out, uint8_t * bytes, int nstreams,
+              const LhMidPools * pools)
 {
     hipemu_dim3 grid = { (unsigned) nstreams, 1, 1 }, block = { LH_BLOCK, 1, 1 };
     LhMidPools const mid = *pools;

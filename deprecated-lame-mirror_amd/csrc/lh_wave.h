@@ -19,7 +19,6 @@
  * path falls through its branch (a taken scalar branch costs ~28 cycles, one that falls through ~14:
  * tools/ubench/branch_cost.hip) */
 #define LH_RARE(x) __builtin_expect(!!(x), 0)
-#define LH_OFTEN(x) __builtin_expect(!!(x), 1)
 
 #ifdef LH_EMU
 /* ------------------------------------------------------------------ */
@@ -39,16 +38,6 @@ lh_wave_sum_u32(uint32_t v)
     uint32_t s = 0;
     for (int i = 0; i < 64; i++)
         s += (uint32_t) x[i];
-    return s;
-}
-
-static inline uint64_t
-lh_wave_sum_u64(uint64_t v)
-{
-    const uint64_t *x = hipemu_wave_exchange(v);
-    uint64_t s = 0;
-    for (int i = 0; i < 64; i++)
-        s += x[i];
     return s;
 }
 

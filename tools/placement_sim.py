@@ -1,6 +1,9 @@
 #!/usr/bin/env python
-"""Would placing streams on CUs by their cost pay?  Needs an LH_PROF build WITHOUT the issue-priority code (-DLH_NO_PRIO), so
-that a stream's cycles show its own cost:  LAMEHIP_LIB=.../liblamehip_profnp.so python tools/placement_sim.py [seconds] [prefix_seconds]
+"""Would placing streams on CUs by their cost pay?  Needs the LH_PROF build (`make prof' in csrc):
+LAMEHIP_LIB=.../liblamehip_prof.so python tools/placement_sim.py [seconds] [prefix_seconds]
+It was written against a profiling build WITHOUT the issue-priority code (lh_prio_*, lh_kernels.hip), so that a stream's
+cycles showed its own cost; the sources have no switch for that (the -DLH_NO_PRIO this text used to ask for does not exist),
+so today's figures include what the priorities do to a stream -- take that code out by hand for a clean reading.
 Prints how well the search-call counters of a prefix predict a stream's cost, and the spread of CU-group means for the
 dispatcher's grouping (workgroup id mod 256) against a snake placement by predicted cost."""
 import ctypes as C
