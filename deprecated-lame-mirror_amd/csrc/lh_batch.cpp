@@ -10,6 +10,8 @@
 
 #include "lh_api_int.h"
 #include "lh_pcm_in.h"
+#include "lh_gain.h"
+#include "lh_replaygain_tables.h"
 
 extern "C" int lh_launch_resample_typed(int type, const LhRsParams * p, const float *bank, const LhRsBlock * trunk, const LhRsBlock * tails,
                                         const LhRsStream * streams, int nstreams, int max_blocks, const void *pcm, float *pcmf,
@@ -17,6 +19,8 @@ extern "C" int lh_launch_resample_typed(int type, const LhRsParams * p, const fl
 extern "C" int lh_launch_ingest(int type, const LhInParams * p, const LhInStream * streams, int nstreams, long long max_n, const void *in,
                                 float *out, void *stream);
 extern "C" int lh_launch_deinterleave(int esz, const void *src_l, const void *src_r, void *dst_l, void *dst_r, long long n, void *stream);
+extern "C" int lh_launch_gain(int floats, const LhGainParams * p, const LhGainStream * streams, int nstreams, const int *trunk, const int *tails,
+                              const void *pool, double *pairs, void *stream);
 extern "C" void lh_pcm_copy_plane(void *dst, const void *src, int esz, int stride, long n);
 
 /* per device: the end of the last launch that filled it (lamehip_batch_encode) */
@@ -113,6 +117,25 @@ struct lamehip_batch {
     LhEvent ev_rs[2];
     int     rs_ran = 0;         /* the last lamehip_batch_encode converted something (between ev_rs[0] and ev_rs[1]) */
     float   rs_ms = 0;
+    /* ReplayGain (lamehip_batch_set_replaygain): lamehip_batch_encode measures the radio gain of the streams declared since
+     * their last analysis with lh_gain.hip, behind the conversion / ingest kernels and in front of the analysis kernels.  The
+     * host plans (lh_gain_plan: the blocks the handle API would hand to lh_rg_block), the kernel leaves every stream's window
+     * sums in rg_pairs, and the first getter brings them to rg_win, where bins and gain are made of them (lh_replaygain.c). */
+    int     rg_on = 0;
+    int     rg_measured = 0;    /* an encode with the switch on has run since the last reset */
+    int     rg_pending = 0;     /* the last launch's window sums are still on the device */
+    std::vector < char >rg_dirty;       /* declared since the stream's last analysis */
+    std::vector < long >rg_len_in;      /* a batch that converts on the host: input samples behind len[] */
+    std::vector < std::vector < double > >rg_win;       /* per stream: (lsum, rsum) per finished window */
+    std::vector < int >rg_tenths;
+    std::vector < LhGainStream > h_rg_streams;
+    std::vector < int >h_rg_tails, h_rg_trunk;
+    LhDevBuf < LhGainStream > d_rg_streams;
+    LhDevBuf < int >d_rg_tails, d_rg_trunk;
+    LhDevBuf < double >d_rg_pairs;
+    LhEvent ev_rg[2];
+    int     rg_ran = 0;         /* the last lamehip_batch_encode analysed something (between ev_rg[0] and ev_rg[1]) */
+    float   rg_ms = 0;
     /* incremental use (lamehip_batch_append ...): samples in the pool / frames encoded per stream, a
      * packer and the bytes not yet drained per stream, and the pinned staging area of the next
      * lamehip_batch_encode_available (see h_stage below) */
@@ -463,6 +486,8 @@ lamehip_batch_create_on(int device, const lame_t proto, int nstreams, long capac
     b->bytes_off.assign((size_t) nstreams, 0);
     b->padding.assign((size_t) nstreams, 0);
     b->row_dirty.assign((size_t) nstreams, 0);
+    b->rg_dirty.assign((size_t) nstreams, 0);
+    b->rg_len_in.assign((size_t) nstreams, 0);
     b->split = batch_use_split();
     if (proto->rs) {
         /* the s16 pool shrinks to nothing, the converted signal (plus the flush's tail) lives in a float pool */
@@ -567,6 +592,7 @@ lamehip_batch_set_length(lamehip_batch * b, int s, long n)
         return -1;
     }
     b->pcm_given = 1;
+    b->rg_dirty[(size_t) s] = 1;        /* declared: the stream's gain is measured again */
     if (b->dev_rs)
         return batch_plan_stream(b, s, n);
     if (b->stype != LH_PCM_S16)
@@ -599,6 +625,8 @@ batch_convert_stream(lamehip_batch * b, int s, const short *l, const short *r, l
     b->len[(size_t) s] = conv;
     b->nframes[(size_t) s] = frames;
     b->padding[(size_t) s] = padding;
+    b->rg_len_in[(size_t) s] = n;
+    b->rg_dirty[(size_t) s] = 1;
     hipError_t e = hipSuccess;
     if (conv > 0) {
         e = hipMemcpy(b->d_pcmf.get() + ((size_t) s * 2) * (size_t) b->capf, ol, (size_t) conv * sizeof(float), hipMemcpyHostToDevice);
@@ -717,6 +745,7 @@ lamehip_batch_mark_pcm(lamehip_batch * b, int s)
 {
     if (!b || s < 0 || s >= b->B || !b->h_pcm.get())
         return -1;
+    b->rg_dirty[(size_t) s] = 1;        /* new samples: the stream's gain is measured again */
     if (b->dev_rs)
         b->rs_dirty[(size_t) s] = 1;    /* new samples: the stream is converted again */
     else if (b->stype != LH_PCM_S16)
@@ -939,6 +968,16 @@ batch_incremental_begin(lamehip_batch * b)
     return 0;
 }
 
+/* a batch that measures ReplayGain is encoded whole (lamehip_batch_encode): the analysis runs once per stream */
+static int
+batch_refuse_gain(const lamehip_batch * b, const char *who)
+{
+    if (!b->rg_on)
+        return 0;
+    snprintf(g_err, sizeof(g_err), "%s: this batch measures ReplayGain (lamehip_batch_set_replaygain), which incremental use does not", who);
+    return 1;
+}
+
 #define LH_STAGE_SEGS 4096       /* chunks per trip to HBM */
 #define LH_STAGE_SAMPLES (8L << 20)     /* the arena: 8 M samples = 16 MB; what is staged beyond goes to HBM at once */
 
@@ -1000,6 +1039,8 @@ lamehip_batch_append(lamehip_batch * b, int s, const short *l, const short *r, i
         snprintf(g_err, sizeof(g_err), "lamehip_batch_append: the batch is finished (lamehip_batch_reset starts it over)");
         return -1;
     }
+    if (batch_refuse_gain(b, "lamehip_batch_append"))
+        return -1;
     if ((rc = batch_incremental_begin(b)) != 0)
         return rc;
     if (n == 0)
@@ -1125,6 +1166,8 @@ lamehip_batch_encode_available(lamehip_batch * b)
         snprintf(g_err, sizeof(g_err), "lamehip_batch_encode_available: the batch is finished (lamehip_batch_reset starts it over)");
         return -1;
     }
+    if (batch_refuse_gain(b, "lamehip_batch_encode_available"))
+        return -1;
     if ((rc = batch_incremental_begin(b)) != 0)
         return rc;
     if ((rc = batch_stage_reserve(b)) != 0)
@@ -1149,6 +1192,8 @@ lamehip_batch_finish(lamehip_batch * b)
         snprintf(g_err, sizeof(g_err), "lamehip_batch_finish: the batch is finished already (lamehip_batch_reset starts it over)");
         return -1;
     }
+    if (batch_refuse_gain(b, "lamehip_batch_finish"))
+        return -1;
     if ((rc = batch_incremental_begin(b)) != 0)
         return rc;
     if ((rc = batch_stage_reserve(b)) != 0)
@@ -1224,6 +1269,14 @@ lamehip_batch_reset(lamehip_batch * b)
         b->stage_nseg = 0;
         b->finished = 0;
     }
+    /* every gain is forgotten, and every stream with it: the next encode measures all of them again */
+    b->rg_measured = 0;
+    b->rg_pending = 0;
+    b->rg_ran = 0;
+    b->rg_ms = 0;
+    for (std::vector < double >&w:b->rg_win)
+        w.clear();
+    b->rg_dirty.assign((size_t) b->B, 1);
     return batch_reset_states(b);
 }
 
@@ -1334,6 +1387,268 @@ batch_ingest_launch(lamehip_batch * b)
     return 0;
 }
 
+/* ---- ReplayGain of a batch: the radio gain of every stream, measured by lh_gain.hip inside lamehip_batch_encode ---- */
+
+static long
+batch_gain_window(const lamehip_batch * b)
+{
+    return (b->cfg.samplerate * 1L + 20L - 1) / 20L;    /* 50 ms at the output rate, rounded up (lh_rg_start) */
+}
+
+/* the last launch's window sums come home: per stream the pairs, and the gain lh_replaygain.c makes of them */
+static int
+batch_gain_fetch(lamehip_batch * b)
+{
+    long const W = batch_gain_window(b);
+    long long wins = 0;
+    if (!b->rg_pending)
+        return 0;
+    for (const LhGainStream & d:b->h_rg_streams)
+        wins += d.total / W;
+    std::vector < double >all((size_t) (2 * wins));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (wins > 0)
+        HIPCHK(hipMemcpy(all.data(), b->d_rg_pairs.get(), all.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (const LhGainStream & d:b->h_rg_streams) {
+        long const nw = d.total / W;
+        std::vector < double >&w = b->rg_win[(size_t) d.stream];
+        w.assign(all.begin() + 2 * d.win_at, all.begin() + 2 * (d.win_at + nw));
+        b->rg_tenths[(size_t) d.stream] = lh_gain_from_windows(w.data(), nw, W);
+    }
+    b->rg_pending = 0;
+    return 0;
+}
+
+/* The streams declared since their last analysis go through the gain kernel, on the batch's stream: the host plans --
+ * which blocks the handle API would have handed to lh_rg_block, from the lengths alone --, the plan travels, one launch. */
+static int
+batch_gain_launch(lamehip_batch * b)
+{
+    int const fs = fs_of(b->cfg), mfn = mfn_of(b->cfg);
+    long const W = batch_gain_window(b);
+    long long wins = 0;
+    int     max_trunk = 0;
+    LhResampler *host_rs = nullptr;
+    /* (the pairs of the launch before this one share the buffer) */
+    if (batch_gain_fetch(b) != 0)
+        return LAMEHIP_ERR_DEVICE;
+    b->h_rg_streams.clear();
+    b->h_rg_tails.clear();
+    for (int s = 0; s < b->B; s++) {
+        if (!b->rg_dirty[(size_t) s])
+            continue;
+        LhGainStream d;
+        long    total = 0;
+        memset(&d, 0, sizeof(d));
+        d.n = b->len[(size_t) s];
+        d.stream = s;
+        d.win_at = wins;
+        d.tail_at = (int) b->h_rg_tails.size();
+        if (b->dev_rs) {
+            /* the made counts of the stream's conversion plan: the trunk all streams share, then its own tail */
+            d.ntrunk = b->trunk.after[b->len_in[(size_t) s] / b->trunk.fs].nblk;
+            for (const LhRsBlock & k:b->tail[(size_t) s])
+                b->h_rg_tails.push_back(k.made);
+            total = b->len[(size_t) s];
+        }
+        else {
+            /* no conversion: whole frames' worth from position 0 (not listed), the remainder, the flush's zeros; a batch that
+             * converts on the host: the plan of the conversion it made in lamehip_batch_set_pcm, listed whole */
+            long const n_in = b->rate_in ? b->rg_len_in[(size_t) s] : b->len[(size_t) s];
+            if (b->rate_in && !host_rs) {
+                host_rs = (LhResampler *) malloc(sizeof(LhResampler));
+                if (!host_rs) {
+                    snprintf(g_err, sizeof(g_err), "out of memory (gain plan)");
+                    return -2;
+                }
+                lh_rs_init(host_rs, b->rate_in, b->cfg.samplerate);
+            }
+            std::vector < int >blocks(64);
+            /* (a stream of a converting batch that was never handed over has no converted signal, not even a flush's) */
+            bool const none = b->rate_in && b->len[(size_t) s] == 0;
+            int     nb = none ? 0 : lh_gain_plan(host_rs, fs, mfn, n_in, blocks.data(), (int) blocks.size(), &total);
+            if (nb > (int) blocks.size()) {
+                blocks.resize((size_t) nb);
+                nb = lh_gain_plan(host_rs, fs, mfn, n_in, blocks.data(), (int) blocks.size(), &total);
+            }
+            if (nb < 0 || (b->rate_in && total != b->len[(size_t) s])) {
+                free(host_rs);
+                snprintf(g_err, sizeof(g_err), "gain plan: stream %d's blocks do not add up to its length", s);
+                return -1;
+            }
+            d.ntrunk = b->rate_in ? 0 : (int) (n_in / fs);
+            b->h_rg_tails.insert(b->h_rg_tails.end(), blocks.begin() + d.ntrunk, blocks.begin() + nb);
+        }
+        if (total > LH_GN_MAX_TOTAL) {
+            free(host_rs);
+            snprintf(g_err, sizeof(g_err), "lamehip_batch_encode: stream %d is too long for the ReplayGain analysis (%ld samples)", s, total);
+            return -1;
+        }
+        d.total = (int) total;
+        d.ntail = (int) b->h_rg_tails.size() - d.tail_at;
+        if (b->dev_rs && d.ntrunk > max_trunk)
+            max_trunk = d.ntrunk;
+        wins += total / W;
+        b->h_rg_streams.push_back(d);
+    }
+    free(host_rs);
+    if (b->h_rg_streams.empty()) {
+        b->rg_measured = 1;     /* (nothing declared since the last analysis: every result stands) */
+        return 0;
+    }
+    b->h_rg_trunk.resize((size_t) max_trunk);
+    for (int j = 0; j < max_trunk; j++)
+        b->h_rg_trunk[(size_t) j] = b->trunk.blk[j].made;
+    /* (drained first: the analysis of the previous round may still be reading the old buffers) */
+    HIPCHK(b->d_rg_tails.reserve(b->h_rg_tails.size() + 1, 64, b->stream));
+    HIPCHK(b->d_rg_trunk.reserve(b->h_rg_trunk.size() + 1, b->h_rg_trunk.size(), b->stream));
+    HIPCHK(b->d_rg_pairs.reserve((size_t) (2 * wins + 2), (size_t) (wins / 4), b->stream));
+    if (!b->h_rg_tails.empty())
+        HIPCHK(hipMemcpyAsync(b->d_rg_tails.get(), b->h_rg_tails.data(), b->h_rg_tails.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    if (!b->h_rg_trunk.empty())
+        HIPCHK(hipMemcpyAsync(b->d_rg_trunk.get(), b->h_rg_trunk.data(), b->h_rg_trunk.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemcpyAsync(b->d_rg_streams.get(), b->h_rg_streams.data(), b->h_rg_streams.size() * sizeof(LhGainStream), hipMemcpyHostToDevice,
+                          b->stream));
+    LhGainParams p;
+    LhReplayGain probe;         /* (only for the row of the filter tables) */
+    memset(&p, 0, sizeof(p));
+    if (lh_rg_start(&probe, b->cfg.samplerate) != 0)
+        return -1;
+    memcpy(p.ky, lh_rg_yule[probe.rate_index], sizeof(p.ky));
+    memcpy(p.kb, lh_rg_butter[probe.rate_index], sizeof(p.kb));
+    p.m = lh_rs_matrix(b->cfg.pcm_scale, b->cfg.pcm_mix, b->cfg.pcm_scale_r);
+    p.cap = batch_reads_floats(b) ? b->capf : b->cap;
+    p.window = (int) W;
+    p.fs = fs;
+    p.channels = b->cfg.channels;
+    p.one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
+    {
+        /* the mapping of the first filter's feedback, by the size of the launch (LH_GN_TAPS_BELOW: the faster one either side);
+         * LAMEHIP_GAIN_LANES=0 / 1 (measurement aid, tools/replaygain_bench.py) forces the taps across the lanes of a row / the
+         * feedback in lanes 0 and 1 -- the same sums either way */
+        const char *e = getenv("LAMEHIP_GAIN_LANES");
+        p.taps = e ? atoi(e) != 1 : (int) b->h_rg_streams.size() < LH_GN_TAPS_BELOW;
+    }
+    HIPCHK(hipEventRecord(b->ev_rg[0], b->stream));
+    int const rc = lh_launch_gain(batch_reads_floats(b), &p, b->d_rg_streams.get(), (int) b->h_rg_streams.size(),
+                                  b->dev_rs ? b->d_rg_trunk.get() : nullptr, b->d_rg_tails.get(),
+                                  batch_reads_floats(b) ? (const void *) b->d_pcmf.get() : (const void *) b->d_pcm.get(), b->d_rg_pairs.get(),
+                                  (void *) (hipStream_t) b->stream);
+    if (rc)
+        return set_err("gain launch", (hipError_t) rc);
+    HIPCHK(hipEventRecord(b->ev_rg[1], b->stream));
+    /* queued: only now do the streams count as analysed (a failure above leaves them declared, and the getters refusing) */
+    b->rg_dirty.assign((size_t) b->B, 0);
+    b->rg_measured = 1;
+    b->rg_ran = 1;
+    b->rg_pending = 1;
+    return 0;
+}
+
+/* the tag of stream s carries its gain when the batch measures it */
+static int
+batch_tag_gain(lamehip_batch * b, int s, LhVbrTag * v)
+{
+    LhDeviceScope const on_device(b->device);
+    if (!b->rg_on || !b->rg_measured)
+        return 0;
+    if (batch_gain_fetch(b) != 0)
+        return LAMEHIP_ERR_DEVICE;
+    v->radio_gain_on = 1;
+    v->radio_gain = b->rg_tenths[(size_t) s];
+    return 0;
+}
+
+/* ReplayGain for every stream of the batch: lamehip_batch_encode measures the radio gain the handle API would report for
+ * the same samples fed a frame's worth per lame_encode_buffer call (lame_set_findReplayGain), and the tagged outputs
+ * carry it.  Before lamehip_batch_encode; not for incremental batches.  The proto's own setting is not inherited. */
+extern "C" int
+lamehip_batch_set_replaygain(lamehip_batch * b, int on)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b)
+        return -1;
+    if (b->incremental) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_replaygain: this batch is fed with lamehip_batch_append (incremental use)");
+        return -1;
+    }
+    if (!on || b->rg_on) {
+        b->rg_on = on != 0 && b->rg_on;
+        return 0;
+    }
+    /* everything new first: a failure leaves the batch as it was */
+    LhDevBuf < LhGainStream > streams;
+    LhEvent ev[2];
+    hipError_t e = streams.alloc((size_t) b->B);
+    if (e == hipSuccess)
+        e = ev[0].create();
+    if (e == hipSuccess)
+        e = ev[1].create();
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        return set_err("lamehip_batch_set_replaygain: device allocation", e);
+    }
+    b->d_rg_streams = std::move(streams);
+    b->ev_rg[0] = std::move(ev[0]);
+    b->ev_rg[1] = std::move(ev[1]);
+    b->rg_win.assign((size_t) b->B, std::vector < double >());
+    b->rg_tenths.assign((size_t) b->B, 0);
+    b->rg_dirty.assign((size_t) b->B, 1);       /* whatever has been declared so far is measured by the next encode */
+    b->rg_measured = 0;
+    b->rg_pending = 0;
+    b->rg_on = 1;
+    return 0;
+}
+
+static int
+batch_gain_ready(lamehip_batch * b, int s, const char *who)
+{
+    if (!b || s < 0 || s >= b->B)
+        return -1;
+    if (!b->rg_on || !b->rg_measured) {
+        snprintf(g_err, sizeof(g_err), "%s: no lamehip_batch_encode with lamehip_batch_set_replaygain on has run", who);
+        return -1;
+    }
+    return batch_gain_fetch(b) != 0 ? LAMEHIP_ERR_DEVICE : 0;
+}
+
+/* stream s's radio gain in tenths of a dB as the LAME tag stores it (lame_get_RadioGain); 0 when the stream has no
+ * finished window.  Waits for the batch's stream. */
+extern "C" int
+lamehip_batch_radio_gain(lamehip_batch * b, int s, int *tenths_db)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int const rc = tenths_db ? batch_gain_ready(b, s, "lamehip_batch_radio_gain") : -1;
+    if (rc)
+        return rc;
+    *tenths_db = b->rg_tenths[(size_t) s];
+    return 0;
+}
+
+/* test accessor: the window sums the kernel left for stream s, (lsum, rsum) per finished 50 ms window; writes the first
+ * cap_windows pairs and returns the number of windows, or a negative code */
+extern "C" long
+lamehip_batch_get_gain_windows(lamehip_batch * b, int s, double *lr_pairs, long cap_windows)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int const rc = batch_gain_ready(b, s, "lamehip_batch_get_gain_windows");
+    if (rc)
+        return rc;
+    std::vector < double >const &w = b->rg_win[(size_t) s];
+    long const nw = (long) (w.size() / 2), k = nw < cap_windows ? nw : cap_windows;
+    if (k > 0 && lr_pairs)
+        memcpy(lr_pairs, w.data(), (size_t) k * 2 * sizeof(double));
+    return nw;
+}
+
+/* HIP-event time of the gain kernel of the last lamehip_batch_encode (after lamehip_batch_sync); 0 when none ran.  Not part
+ * of lamehip_batch_last_kernel_ms. */
+extern "C" float
+lamehip_batch_last_gain_ms(lamehip_batch * b)
+{
+    return b ? b->rg_ms : 0.0f;
+}
+
 /* The byte pool's slice of stream s (device packing; else 0): room for every frame at the largest frame size the settings
  * allow, +1 for CBR padding.  lamehip_batch_encode lays the streams out with it, lamehip_batch_reserve sizes the pool by it. */
 static long long
@@ -1414,6 +1729,13 @@ lamehip_batch_encode(lamehip_batch * b)
     }
     else if (b->stype != LH_PCM_S16) {
         int const rc = batch_ingest_launch(b);
+        if (rc)
+            return rc;
+    }
+    /* ReplayGain: behind the conversion / ingest, in front of the analysis kernels, once per call whatever the windows */
+    b->rg_ran = 0;
+    if (b->rg_on) {
+        int const rc = batch_gain_launch(b);
         if (rc)
             return rc;
     }
@@ -1738,6 +2060,8 @@ lamehip_batch_get_bytes_tagged(lamehip_batch * b, int s, unsigned char *out, lon
         v.samplerate_in = b->rate_in;
     if (out_size < total)
         return -1;
+    if (batch_tag_gain(b, s, &v) != 0)
+        return LAMEHIP_ERR_DEVICE;
     k = lamehip_batch_get_bytes(b, s, out + total, out_size - total);
     if (k < 0 || total == 0)
         return k;
@@ -1845,6 +2169,11 @@ lamehip_batch_sync(lamehip_batch * b)
         if (b->in_ran && hipEventElapsedTime(&b->in_ms, b->ev_in[0], b->ev_in[1]) != hipSuccess) {
             (void) hipGetLastError();
             b->in_ms = 0;
+        }
+        b->rg_ms = 0;
+        if (b->rg_ran && hipEventElapsedTime(&b->rg_ms, b->ev_rg[0], b->ev_rg[1]) != hipSuccess) {
+            (void) hipGetLastError();
+            b->rg_ms = 0;
         }
         if (hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess)
             b->last_ms = ms;
@@ -2007,6 +2336,8 @@ lamehip_batch_pack_tagged(lamehip_batch * b, int s, unsigned char *out, long out
         v.samplerate_in = b->rate_in;
     if (out_size < total)
         return -1;
+    if (batch_tag_gain(b, s, &v) != 0)
+        return LAMEHIP_ERR_DEVICE;
     n = b->nframes[(size_t) s];
     fr.resize((size_t) n);
     if (lamehip_batch_get_frames(b, s, fr.data(), n) != n)

@@ -220,6 +220,16 @@ typedef struct LhReplayGain {
 int     lh_rg_start(LhReplayGain * g, int samplerate);
 int     lh_rg_block(LhReplayGain * g, const float *l, const float *r, int n, int channels);
 int     lh_rg_finish(LhReplayGain * g);
+/* what lh_rg_block / lh_rg_finish make of a window's sums and of the histogram: one text for the handle's host analysis
+ * and for the window sums a batch's device analysis brings back */
+size_t  lh_rg_bin(double lsum, double rsum, long window);
+int     lh_rg_tenths(const uint32_t * bins);
+int     lh_gain_from_windows(const double *pairs, long nwin, long window);
+/* a batch stream's analysis as a plan -- the blocks lame_encode_buffer would hand to lh_rg_block, from the stream's length
+ * alone; rs == NULL: no rate conversion -- and the plan evaluated on host samples (lh_gain.hip's twin) */
+int     lh_gain_plan(const LhResampler * rs, int fs, int mfn, long n, int *blocks, int cap, long *total);
+long    lh_gain_eval_host(int samplerate, int channels, const int *blocks, int nblocks, const float *l, const float *r, long n,
+                          double *pairs, long cap, int *tenths);
 
 #ifdef __cplusplus
 }

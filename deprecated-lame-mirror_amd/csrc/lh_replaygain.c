@@ -20,6 +20,7 @@
 #include <string.h>
 #include "lh_host.h"
 #include "lh_replaygain_tables.h"
+#include "lh_gain.h"
 
 #define RG_ORDER 10
 
@@ -96,9 +97,21 @@ piece_energy(LhReplayGain * g, int ch, const float *x, int n)
     return sum;
 }
 
-/* one block as lame_encode_buffer hands it to the analysis (at most one frame's worth of samples) */
-int
-lh_rg_block(LhReplayGain * g, const float *l, const float *r, int n, int channels)
+/* the histogram bin of a finished window: its mean square in 0.01 dB steps, truncated (the one place a log10 is taken:
+ * the batch's device analysis hands its window sums to this very text) */
+size_t
+lh_rg_bin(double lsum, double rsum, long window)
+{
+    double const level = 100 * 10. * log10((lsum + rsum) / window * 0.5 + 1.e-37);
+    size_t  bin = (level <= 0) ? 0 : (size_t) level;
+    if (bin >= LH_RG_BINS)
+        bin = LH_RG_BINS - 1;
+    return bin;
+}
+
+/* one block; with `nwin', finished windows are counted there and their sums kept in pairs[2 k], pairs[2 k + 1] for k < cap */
+static int
+rg_block(LhReplayGain * g, const float *l, const float *r, int n, int channels, double *pairs, long cap, long *nwin)
 {
     int     at = 0;
     if (g->rate_index < 0 || n <= 0)
@@ -118,11 +131,14 @@ lh_rg_block(LhReplayGain * g, const float *l, const float *r, int n, int channel
         at += (int) take;
         g->filled += take;
         if (g->filled == g->window) {
-            double const level = 100 * 10. * log10((g->lsum + g->rsum) / g->filled * 0.5 + 1.e-37);
-            size_t  bin = (level <= 0) ? 0 : (size_t) level;
-            if (bin >= LH_RG_BINS)
-                bin = LH_RG_BINS - 1;
-            g->bins[bin]++;
+            g->bins[lh_rg_bin(g->lsum, g->rsum, g->filled)]++;
+            if (nwin) {
+                if (pairs && *nwin < cap) {
+                    pairs[2 * *nwin] = g->lsum;
+                    pairs[2 * *nwin + 1] = g->rsum;
+                }
+                ++*nwin;
+            }
             g->lsum = g->rsum = 0.;
             g->filled = 0;
         }
@@ -130,29 +146,43 @@ lh_rg_block(LhReplayGain * g, const float *l, const float *r, int n, int channel
     return 0;
 }
 
-/* the title's gain in tenths of a dB as the tag stores it (reference lame.c:1571-1578), 0 when no window was
- * completed; the state is ready for the next title afterwards (--nogap) */
+/* one block as lame_encode_buffer hands it to the analysis (at most one frame's worth of samples) */
 int
-lh_rg_finish(LhReplayGain * g)
+lh_rg_block(LhReplayGain * g, const float *l, const float *r, int n, int channels)
+{
+    return rg_block(g, l, r, n, channels, NULL, 0, NULL);
+}
+
+/* the gain in tenths of a dB as the tag stores it (reference lame.c:1571-1578) that a histogram of windows stands
+ * for: the bin 95 % of them stay below, against the 89 dB reference; 0 when there is no window */
+int
+lh_rg_tenths(const uint32_t * bins)
 {
     unsigned long windows = 0, upper, seen = 0;
     size_t  i;
-    int     tenths = 0;
+    float   gain;
+    for (i = 0; i < LH_RG_BINS; i++)
+        windows += bins[i];
+    if (windows == 0)
+        return 0;
+    upper = (unsigned long) (uint32_t) ceil((uint32_t) windows * (1. - 0.95));
+    for (i = LH_RG_BINS; i-- > 0;) {
+        seen += bins[i];
+        if (seen >= upper)
+            break;
+    }
+    gain = (float) ((float) 64.82 - (float) i / (float) 100);
+    return (int) floor(gain * 10.0 + 0.5);
+}
+
+/* the title's gain, 0 when no window was completed; the state is ready for the next title afterwards (--nogap) */
+int
+lh_rg_finish(LhReplayGain * g)
+{
+    int     tenths;
     if (g->rate_index < 0)
         return 0;
-    for (i = 0; i < LH_RG_BINS; i++)
-        windows += g->bins[i];
-    if (windows != 0) {
-        float   gain;
-        upper = (unsigned long) (uint32_t) ceil((uint32_t) windows * (1. - 0.95));
-        for (i = LH_RG_BINS; i-- > 0;) {
-            seen += g->bins[i];
-            if (seen >= upper)
-                break;
-        }
-        gain = (float) ((float) 64.82 - (float) i / (float) 100);
-        tenths = (int) floor(gain * 10.0 + 0.5);
-    }
+    tenths = lh_rg_tenths(g->bins);
     memset(g->bins, 0, sizeof(g->bins));
     memset(g->hist_in, 0, sizeof(g->hist_in));
     memset(g->hist_mid, 0, sizeof(g->hist_mid));
@@ -160,4 +190,136 @@ lh_rg_finish(LhReplayGain * g)
     g->filled = 0;
     g->lsum = g->rsum = 0.;
     return tenths;
+}
+
+/* the gain of a stream from its window sums: `nwin' pairs (lsum, rsum) of windows of `window' samples */
+int
+lh_gain_from_windows(const double *pairs, long nwin, long window)
+{
+    uint32_t *bins = (uint32_t *) calloc(LH_RG_BINS, sizeof(uint32_t));
+    long    k;
+    int     tenths;
+    if (!bins)
+        return 0;
+    for (k = 0; k < nwin; k++)
+        bins[lh_rg_bin(pairs[2 * k], pairs[2 * k + 1], window)]++;
+    tenths = lh_rg_tenths(bins);
+    free(bins);
+    return tenths;
+}
+
+/* ---- the analysis of a batch's stream as a plan (the device kernel's input, lh_gain.hip) and its host evaluation ----
+ *
+ * lh_gain_plan: the blocks the handle API hands to lh_rg_block for a stream of n input samples fed `fs' samples per
+ * lame_encode_buffer call and flushed, from the length alone.  rs == NULL, no rate conversion: fs samples from position 0
+ * on, the remainder, then the flush's bunches of zeros (lame_encode_flush, lh_api.cpp).  Else the made counts of the
+ * stream's conversion plan (lh_rs_plan: trunk, then tail, flush blocks included).  Returns the number of blocks -- only
+ * the first `cap' are written --, or -1; *total = the samples they add up to. */
+int
+lh_gain_plan(const LhResampler * rs, int fs, int mfn, long n, int *blocks, int cap, long *total)
+{
+    long    sum = 0;
+    int     k = 0;
+    if (n < 0 || fs < 1)
+        return -1;
+    if (rs) {
+        LhRsBlock one, *b = &one;
+        long    conv = 0;
+        int     ntrunk = 0, frames = 0, padding = 0, i;
+        int const nb = lh_rs_plan(rs, fs, mfn, n, b, 1, &ntrunk, &conv, &frames, &padding);
+        if (nb < 0)
+            return -1;
+        if (nb > 1) {
+            b = (LhRsBlock *) malloc((size_t) nb * sizeof(LhRsBlock));
+            if (!b || lh_rs_plan(rs, fs, mfn, n, b, nb, &ntrunk, &conv, &frames, &padding) != nb) {
+                free(b);
+                return -1;
+            }
+        }
+        for (i = 0; i < nb; i++) {
+            if (k < cap)
+                blocks[k] = b[i].made;
+            k++;
+            sum += b[i].made;
+        }
+        if (b != &one)
+            free(b);
+    }
+    else {
+        long    fed, at;
+        long    frames = (n > 0 && LH_MF_START + n >= mfn) ? (LH_MF_START + n - mfn) / fs + 1 : 0;
+        int const owed = (int) (576 + n - (long) fs * frames);
+        int     padding = fs - (owed % fs), frames_left;
+        for (at = 0; at < n; at += fs) {
+            if (k < cap)
+                blocks[k] = (int) (n - at > fs ? fs : n - at);
+            k++;
+        }
+        sum = fed = n;
+        if (padding < 576)
+            padding += fs;
+        frames_left = (owed + padding) / fs;
+        while (frames_left > 0) {
+            int     bunch = mfn - (int) (LH_MF_START + fed - (long) fs * frames);
+            bunch = bunch > 1152 ? 1152 : (bunch < 1 ? 1 : bunch);
+            if (k < cap)
+                blocks[k] = bunch;
+            k++;
+            fed += bunch;
+            sum += bunch;
+            if (LH_MF_START + fed - (long) fs * frames >= mfn) {
+                frames++;
+                frames_left--;
+            }
+        }
+    }
+    if (total)
+        *total = sum;
+    return k;
+}
+
+/* lh_gain_eval_host: a plan evaluated on host samples with lh_rg_block's own arithmetic -- the kernel's twin.  l / r: n
+ * samples as the analysis hears them (behind the PCM matrix; positions from n on are zeros, generated here); channels == 1:
+ * l stands for both.  Writes the first `cap' window pairs, returns the number of windows (or -1) and, with `tenths', the
+ * gain. */
+long
+lh_gain_eval_host(int samplerate, int channels, const int *blocks, int nblocks, const float *l, const float *r, long n,
+                  double *pairs, long cap, int *tenths)
+{
+    LhReplayGain *g = (LhReplayGain *) malloc(sizeof(LhReplayGain));
+    float  *buf = (float *) malloc(2 * LH_RG_MAX_BLOCK * sizeof(float));
+    long    at = 0, nwin = 0;
+    int     i, rc = 0;
+    if (!g || !buf || lh_rg_start(g, samplerate) != 0) {
+        free(g);
+        free(buf);
+        return -1;
+    }
+    for (i = 0; i < nblocks && rc == 0; i++) {
+        int const m = blocks[i];
+        long    have = n - at;
+        if (m <= 0)
+            continue;
+        if (m > LH_RG_MAX_BLOCK) {
+            rc = -1;
+            break;
+        }
+        if (have < 0)
+            have = 0;
+        if (have > m)
+            have = m;
+        memset(buf, 0, 2 * LH_RG_MAX_BLOCK * sizeof(float));
+        if (have > 0) {
+            memcpy(buf, l + at, (size_t) have * sizeof(float));
+            if (channels != 1)
+                memcpy(buf + LH_RG_MAX_BLOCK, r + at, (size_t) have * sizeof(float));
+        }
+        rc = rg_block(g, buf, buf + LH_RG_MAX_BLOCK, m, channels, pairs, cap, &nwin);
+        at += m;
+    }
+    if (tenths)
+        *tenths = lh_rg_finish(g);
+    free(g);
+    free(buf);
+    return rc ? -1 : nwin;
 }

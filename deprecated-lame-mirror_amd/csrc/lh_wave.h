@@ -212,6 +212,66 @@ lh_row_shr_u32(uint32_t v)
     return (me & 15) >= D ? (uint32_t) x[me - D] : 0u;
 }
 
+/* Row shifts for lh_gain.hip, which does several per sample: an exchange of one barrier instead of two.  Two areas take turns,
+ * so that a fiber that writes exchange k + 1 never touches what a slower fiber still reads of exchange k; nobody reaches
+ * exchange k + 2 -- the same area again -- before all have passed the barrier of k + 1, that is finished reading k. */
+static inline const uint64_t *
+lh_emu_swap(uint64_t v)
+{
+    static uint64_t area[2][64][64];
+    static unsigned turn[64][64];
+    int const w = lh_wave_id(), me = lh_lane();
+    unsigned const k = turn[w][me]++ & 1u;
+    area[k][w][me] = v;
+    hipemu_wave_sync();
+    return area[k][w];
+}
+
+/* value of lane + D of the same row of 16 lanes (0 where there is none): the device's row_shl */
+template < int D > static inline float
+lh_row_shl_f32(float v)
+{
+    uint32_t u;
+    float   r = 0.0f;
+    memcpy(&u, &v, 4);
+    const uint64_t *x = lh_emu_swap(u);
+    int const me = lh_lane();
+    if ((me & 15) + D < 16) {
+        u = (uint32_t) x[me + D];
+        memcpy(&r, &u, 4);
+    }
+    return r;
+}
+
+/* value of lane - D of the same row (0 where there is none), a float or a double */
+template < int D > static inline float
+lh_row_shr_f32(float v)
+{
+    uint32_t u;
+    float   r = 0.0f;
+    memcpy(&u, &v, 4);
+    const uint64_t *x = lh_emu_swap(u);
+    int const me = lh_lane();
+    if ((me & 15) >= D) {
+        u = (uint32_t) x[me - D];
+        memcpy(&r, &u, 4);
+    }
+    return r;
+}
+
+template < int D > static inline double
+lh_row_shr_f64(double v)
+{
+    uint64_t u;
+    double  r = 0.0;
+    memcpy(&u, &v, 8);
+    const uint64_t *x = lh_emu_swap(u);
+    int const me = lh_lane();
+    if ((me & 15) >= D)
+        memcpy(&r, &x[me - D], 8);
+    return r;
+}
+
 /* value of the lane below inside a row of 16 lanes (0 for the row's first lane, as on the device) */
 static inline uint32_t
 lh_lane_below_u32(uint32_t v)
@@ -514,6 +574,28 @@ template < int D > __device__ __forceinline__ uint32_t
 lh_row_shr_u32(uint32_t v)
 {
     return lh_dpp < 0x110 + D, 0u > (v);
+}
+
+/* row_shl / row_shr on floats and doubles (lh_gain.hip); 64-bit VALU operations take no general DPP control on this target,
+ * so a double crosses lanes as two 32-bit moves */
+template < int D > __device__ __forceinline__ float
+lh_row_shl_f32(float v)
+{
+    return __uint_as_float(lh_dpp < 0x100 + D, 0u > (__float_as_uint(v)));
+}
+
+template < int D > __device__ __forceinline__ float
+lh_row_shr_f32(float v)
+{
+    return __uint_as_float(lh_dpp < 0x110 + D, 0u > (__float_as_uint(v)));
+}
+
+template < int D > __device__ __forceinline__ double
+lh_row_shr_f64(double v)
+{
+    uint32_t const lo = lh_dpp < 0x110 + D, 0u > ((uint32_t) __double2loint(v));
+    uint32_t const hi = lh_dpp < 0x110 + D, 0u > ((uint32_t) __double2hiint(v));
+    return __hiloint2double((int) hi, (int) lo);
 }
 
 /* value of the lane below (0 for lane 0; within a row of 16, which is all count_bits asks for) */

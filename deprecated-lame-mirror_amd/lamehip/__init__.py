@@ -264,6 +264,41 @@ class Batch:
         """HIP-event time of the last encode()'s ingest kernel (input pool -> float pool), 0 when none ran."""
         return float(self.lib.lamehip_batch_last_ingest_ms(self.b))
 
+    def set_replaygain(self, on=True):
+        """Measure every stream's radio gain inside encode() (one kernel of its own, gain_ms()); pack_tagged() /
+        get_bytes_tagged() then write it into the LAME tag.  Before encode(); not for incremental batches."""
+        self.lib.lamehip_batch_set_replaygain.argtypes = [C.c_void_p, C.c_int]
+        rc = self.lib.lamehip_batch_set_replaygain(self.b, 1 if on else 0)
+        if rc:
+            raise RuntimeError("lamehip_batch_set_replaygain failed (%d): %s" % (rc, last_error()))
+
+    def radio_gain(self, s):
+        """Stream s's radio gain in tenths of a dB, as lame_get_RadioGain reports it (0: no 50 ms window completed)."""
+        self.lib.lamehip_batch_radio_gain.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        v = C.c_int(0)
+        rc = self.lib.lamehip_batch_radio_gain(self.b, s, C.byref(v))
+        if rc:
+            raise RuntimeError("lamehip_batch_radio_gain failed (%d): %s" % (rc, last_error()))
+        return v.value
+
+    def gain_windows(self, s):
+        """What the gain kernel measured for stream s: float64 [windows, 2], the left and right sum of squares of every
+        completed 50 ms window (test accessor)."""
+        self.lib.lamehip_batch_get_gain_windows.restype = C.c_long
+        self.lib.lamehip_batch_get_gain_windows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long]
+        n = self.lib.lamehip_batch_get_gain_windows(self.b, s, None, 0)
+        if n < 0:
+            raise RuntimeError("lamehip_batch_get_gain_windows failed (%d): %s" % (n, last_error()))
+        out = np.zeros((n, 2), dtype=np.float64)
+        assert self.lib.lamehip_batch_get_gain_windows(self.b, s, out.ctypes.data, n) == n
+        return out
+
+    def gain_ms(self):
+        """HIP-event time of the last encode()'s gain kernel, 0 when none ran."""
+        self.lib.lamehip_batch_last_gain_ms.restype = C.c_float
+        self.lib.lamehip_batch_last_gain_ms.argtypes = [C.c_void_p]
+        return float(self.lib.lamehip_batch_last_gain_ms(self.b))
+
     def set_pcm(self, s, left, right=None):
         left = np.ascontiguousarray(left, dtype=np.int16)
         right = left if right is None else np.ascontiguousarray(right, dtype=np.int16)   # mono: not read

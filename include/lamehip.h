@@ -293,6 +293,31 @@ void   *lamehip_batch_input_host_ptr(lamehip_batch *);
  * Like lamehip_batch_last_resample_ms it is not part of lamehip_batch_last_kernel_ms / _parts_ms. */
 float   lamehip_batch_last_ingest_ms(lamehip_batch *);
 
+/* ReplayGain of a batch: with the switch on, lamehip_batch_encode measures every stream's radio gain on the device (one
+ * kernel on the batch's stream, behind the conversion / ingest and in front of the analysis kernels, once per call) for
+ * the streams declared since their last analysis, and lamehip_batch_pack_tagged / _get_bytes_tagged write it into the LAME
+ * tag.  Stream s gets the value lame_get_RadioGain returns on the handle API after lame_encode_flush for the same settings
+ * and the same samples handed over a frame's worth (1152, MPEG-2 / 2.5: 576 input samples) per lame_encode_buffer call
+ * with lame_set_findReplayGain(1).  Call it before lamehip_batch_encode.  The proto's lame_set_findReplayGain is not
+ * inherited.  -1 on an incremental batch, and once it is on lamehip_batch_append / _encode_available / _finish return -1
+ * (lamehip_last_error); LAMEHIP_ERR_DEVICE when an allocation fails, the batch is then as it was.
+ * The window sums of a launch stay on the device until a getter or a tagged output asks for them; a lamehip_batch_encode
+ * that finds those of the launch before it still there fetches them first, and for that WAITS for the batch's stream on the
+ * host.  A caller that pipelines rounds reads the gains of a round (lamehip_batch_radio_gain, after lamehip_batch_sync or
+ * the fetch) before it encodes the next. */
+int     lamehip_batch_set_replaygain(lamehip_batch *, int on);
+/* stream's radio gain in tenths of a dB (0 when not one 50 ms window was completed); waits for the batch's stream.  -1
+ * before a lamehip_batch_encode with the switch on, and again after lamehip_batch_reset. */
+int     lamehip_batch_radio_gain(lamehip_batch *, int stream, int *tenths_db);
+/* test accessor: what the kernel measured, (left sum, right sum) of the squares of every completed window; writes the first
+ * cap_windows pairs and returns the number of windows, or a negative code */
+long    lamehip_batch_get_gain_windows(lamehip_batch *, int stream, double *lr_pairs, long cap_windows);
+/* HIP-event time in ms of the gain kernel of the last lamehip_batch_encode (after lamehip_batch_sync); 0 when none ran.  Like
+ * lamehip_batch_last_resample_ms it is not part of lamehip_batch_last_kernel_ms / _parts_ms.  (The kernel has two mappings
+ * of its serial part with the same results; the number of streams in a launch picks the faster, environment
+ * LAMEHIP_GAIN_LANES=0 / 1 forces one: measurement, tests.) */
+float   lamehip_batch_last_gain_ms(lamehip_batch *);
+
 /* Incremental use -- lame_encode_buffer (lame.h:715-722, lame.c:1672-1775) for all streams of a batch at once:
  *   lamehip_batch_append            stage n more samples of one stream (host, pinned memory; any n >= 0, ragged
  *                                   across streams; several calls per stream may precede one encode)
