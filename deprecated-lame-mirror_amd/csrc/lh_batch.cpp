@@ -18,6 +18,7 @@ extern "C" int lh_launch_resample_typed(int type, const LhRsParams * p, const fl
                                         void *stream);
 extern "C" int lh_launch_ingest(int type, const LhInParams * p, const LhInStream * streams, int nstreams, long long max_n, const void *in,
                                 float *out, void *stream);
+extern "C" int lh_launch_append(int type, const LhInParams * p, const LhApSeg * segs, int nsegs, long long max_n, void *pool, void *stream);
 extern "C" int lh_launch_deinterleave(int esz, const void *src_l, const void *src_r, void *dst_l, void *dst_r, long long n, void *stream);
 extern "C" int lh_launch_gain(int floats, const LhGainParams * p, const LhGainStream * streams, int nstreams, const int *trunk, const int *tails,
                               const void *pool, double *pairs, void *stream);
@@ -151,10 +152,20 @@ struct lamehip_batch {
     LhPinned < unsigned char >h_stage;
     LhDevBuf < unsigned char >d_stage;
     long    stage_arena_at = 0; /* byte offset of the arena */
-    long    stage_cap = 0;      /* samples the arena holds */
-    long    stage_used = 0;     /* samples staged */
-    int     stage_nseg = 0;     /* chunks staged */
+    long    stage_cap = 0;      /* shorts the arena holds (a 4-byte element of lamehip_batch_append_input counts as two) */
+    long    stage_used = 0;     /* shorts staged */
+    int     stage_nseg = 0;     /* chunks staged by lamehip_batch_append */
     int     finished = 0;       /* lamehip_batch_finish has run: the streams are closed */
+    /* typed and device-resident appends (lamehip_batch_append_input / _append_input_device / _append_device): the table of
+     * segments lh_append_kernel works through, pinned and in HBM -- entries [0, LH_STAGE_SEGS) for the chunks staged in the
+     * arena, the B behind them for a round that comes from device buffers --, and the events around its launches */
+    LhPinned < LhApSeg > h_ap;
+    LhDevBuf < LhApSeg > d_ap;
+    int     ap_nseg = 0;        /* chunks staged by lamehip_batch_append_input */
+    long long ap_max_n = 0;     /* the longest of them */
+    LhEvent ev_ap[2];
+    int     ap_timed = 0;       /* ev_ap[] are around a launch whose time is not part of ap_ms yet */
+    float   ap_ms = 0;          /* append launches since, and including, the last lamehip_batch_encode_available / _finish */
     std::vector < LhFrameOut > h_new;
     /* pinned host side of a pipelined batch (lamehip_batch_pcm_host_ptr / _upload / _fetch): the mirror of the
      * s16 pool the caller (or lamehip_batch_set_pcm) writes, which reaches HBM with one asynchronous copy on
@@ -940,18 +951,34 @@ lamehip_batch_pcm_device_ptr(lamehip_batch * b)
  * them, lamehip_batch_drain hands a stream's new bytes over -- the bytes lame_encode_buffer would
  * have returned for the same calls --, lamehip_batch_finish is lame_encode_flush for all streams. */
 static int
-batch_incremental_begin(lamehip_batch * b)
+batch_incremental_check(const lamehip_batch * b, const char *who, int typed_ok)
 {
     if (b->incremental)
         return 0;
-    if (b->stype != LH_PCM_S16) {
-        snprintf(g_err, sizeof(g_err), "lamehip_batch_append: incremental batches are s16, this batch's sample type is not (lamehip_batch_set_input)");
+    /* (typed_ok: entered through lamehip_batch_append_input / _append_input_device / _append_device, which take the batch's
+     * own element type) */
+    if (b->stype != LH_PCM_S16 && !typed_ok) {
+        snprintf(g_err, sizeof(g_err), "%s: lamehip_batch_append and what follows it start an s16 batch, this batch's sample type is not s16 "
+                 "(lamehip_batch_append_input takes its samples)", who);
         return -1;
     }
+    /* (how the reference converts the rate depends on how it is called, chunk by chunk: the conversion plan of a batch is
+     * made for whole streams) */
     if (b->rate_in || b->dev_pack) {
-        snprintf(g_err, sizeof(g_err), "incremental batches take the encoder's own input rate and the host packer");
+        snprintf(g_err, sizeof(g_err), "%s: incremental batches take the encoder's own input rate and the host packer, this batch %s", who,
+                 b->rate_in ? "converts the sample rate" : "packs on the device (lamehip_batch_set_device_packing)");
         return -1;
     }
+    return 0;
+}
+
+static int
+batch_incremental_begin(lamehip_batch * b, const char *who, int typed_ok)
+{
+    if (b->incremental)
+        return 0;
+    if (batch_incremental_check(b, who, typed_ok) != 0)
+        return -1;
     if (batch_reset_states(b) != 0)
         return LAMEHIP_ERR_DEVICE;
     b->fed.assign((size_t) b->B, 0);
@@ -1000,30 +1027,108 @@ batch_stage_reserve(lamehip_batch * b)
     return 0;
 }
 
+/* the segment table of the typed / device-resident appends and the events around their launches, made once */
+static int
+batch_append_reserve(lamehip_batch * b)
+{
+    size_t const n = (size_t) LH_STAGE_SEGS + (size_t) b->B;
+    LhPinned < LhApSeg > h;
+    LhDevBuf < LhApSeg > d;
+    LhEvent ev[2];
+    if (b->h_ap.get())
+        return 0;
+    /* everything new first: a failure leaves the batch as it was */
+    hipError_t e = h.alloc(n);
+    if (e == hipSuccess)
+        e = d.alloc(n);
+    if (e == hipSuccess)
+        e = ev[0].create();
+    if (e == hipSuccess)
+        e = ev[1].create();
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        return set_err("append table allocation", e);
+    }
+    b->h_ap = std::move(h);
+    b->d_ap = std::move(d);
+    b->ev_ap[0] = std::move(ev[0]);
+    b->ev_ap[1] = std::move(ev[1]);
+    return 0;
+}
+
+/* the time of the append launch ev_ap[] are around joins ap_ms (the launch has finished, or is waited for here) */
+static void
+batch_append_time(lamehip_batch * b)
+{
+    float   ms = 0;
+    if (!b->ap_timed)
+        return;
+    b->ap_timed = 0;
+    if (hipEventSynchronize(b->ev_ap[1]) == hipSuccess && hipEventElapsedTime(&ms, b->ev_ap[0], b->ev_ap[1]) == hipSuccess)
+        b->ap_ms += ms;
+    else
+        (void) hipGetLastError();
+}
+
+/* nsegs entries of the table at `segs' (HBM), the longest of max_n samples, go to the pool the kernels read -- the float
+ * pool of a typed batch, through lame_copy_inbuffer's arithmetic, or the s16 pool as they are --: one launch of
+ * lh_append_kernel on the batch's stream, between ev_ap[0] and ev_ap[1] */
+static int
+batch_append_launch(lamehip_batch * b, const LhApSeg * segs, int nsegs, long long max_n)
+{
+    LhInParams p;
+    if (nsegs <= 0 || max_n <= 0)
+        return 0;
+    batch_append_time(b);       /* (the events are about to be recorded again) */
+    memset(&p, 0, sizeof(p));
+    p.m = lh_pcm_matrix(b->stype, b->cfg.pcm_scale, b->cfg.pcm_mix, b->cfg.pcm_scale_r);
+    p.channels = b->cfg.channels;
+    p.one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
+    p.cap = b->cap;
+    HIPCHK(hipEventRecord(b->ev_ap[0], b->stream));
+    int const rc = lh_launch_append(b->stype, &p, segs, nsegs, max_n,
+                                    b->stype == LH_PCM_S16 ? (void *) b->d_pcm.get() : (void *) b->d_pcmf.get(), (void *) (hipStream_t) b->stream);
+    if (rc)
+        return set_err("append launch", (hipError_t) rc);
+    HIPCHK(hipEventRecord(b->ev_ap[1], b->stream));
+    b->ap_timed = 1;
+    return 0;
+}
+
 /* what is staged goes to the pool: one copy of the chunk table and of the arena's bytes in use, one scatter
  * launch; wait = the arena is free again on return (it is about to be refilled) */
 static int
 batch_stage_flush(lamehip_batch * b, int wait)
 {
     size_t const segs_at = (size_t) b->B * sizeof(LhStreamDesc);
-    if (b->stage_nseg > 0) {
+    if (b->stage_nseg > 0 || b->ap_nseg > 0) {
         int     rc;
-        HIPCHK(hipMemcpyAsync(b->d_stage.get() + segs_at, b->h_stage.get() + segs_at, (size_t) b->stage_nseg * 16, hipMemcpyHostToDevice,
-                              b->stream));
+        if (b->stage_nseg > 0)
+            HIPCHK(hipMemcpyAsync(b->d_stage.get() + segs_at, b->h_stage.get() + segs_at, (size_t) b->stage_nseg * 16, hipMemcpyHostToDevice,
+                                  b->stream));
+        if (b->ap_nseg > 0)
+            HIPCHK(hipMemcpyAsync(b->d_ap.get(), b->h_ap.get(), (size_t) b->ap_nseg * sizeof(LhApSeg), hipMemcpyHostToDevice, b->stream));
         HIPCHK(hipMemcpyAsync(b->d_stage.get() + b->stage_arena_at, b->h_stage.get() + b->stage_arena_at, (size_t) b->stage_used * 2,
                               hipMemcpyHostToDevice, b->stream));
         rc = lh_launch_scatter((const int16_t *) (b->d_stage.get() + b->stage_arena_at), b->d_pcm.get(), b->cap,
                                (const int *) (b->d_stage.get() + segs_at), b->stage_nseg, (void *) (hipStream_t) b->stream);
         if (rc)
             return set_err("scatter launch", (hipError_t) rc);
+        /* (the chunks of lamehip_batch_append_input: other places of the rows than the scatter's) */
+        if (b->ap_nseg > 0 && (rc = batch_append_launch(b, b->d_ap.get(), b->ap_nseg, b->ap_max_n)) != 0)
+            return rc;
+        b->ap_nseg = 0;
+        b->ap_max_n = 0;
         for (int s = 0; s < b->B; s++) {
             b->fed[(size_t) s] += b->staged[(size_t) s];
             b->staged[(size_t) s] = 0;
         }
         b->stage_nseg = 0;
         b->stage_used = 0;
-        if (wait)
+        if (wait) {
             HIPCHK(hipStreamSynchronize(b->stream));
+            batch_append_time(b);
+        }
     }
     return 0;
 }
@@ -1041,7 +1146,11 @@ lamehip_batch_append(lamehip_batch * b, int s, const short *l, const short *r, i
     }
     if (batch_refuse_gain(b, "lamehip_batch_append"))
         return -1;
-    if ((rc = batch_incremental_begin(b)) != 0)
+    if (b->stype != LH_PCM_S16) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_append: takes s16, this batch's sample type is not (lamehip_batch_append_input takes its samples)");
+        return -1;
+    }
+    if ((rc = batch_incremental_begin(b, "lamehip_batch_append", 0)) != 0)
         return rc;
     if (n == 0)
         return 0;
@@ -1078,6 +1187,218 @@ lamehip_batch_append(lamehip_batch * b, int s, const short *l, const short *r, i
         n -= piece;
     }
     return 0;
+}
+
+/* ---- appends in the batch's own element type, from host memory or from HBM (any sample type; csrc/lh_ingest.hip:
+ * lh_append_kernel).  A chunk's place in its stream's rows is fixed when it is appended, fed + staged: a chunk staged in
+ * the arena is counted in `staged' until it leaves for HBM, one that comes from device buffers is in the pool when the call
+ * returns and counted in `fed' at once -- so the two kinds may follow each other in any order and land disjointly. ---- */
+
+/* what the three calls check and make ready before they touch anything: 0, or the call's return value */
+static int
+batch_append_enter(lamehip_batch * b, const char *who, int stride)
+{
+    int     rc;
+    if (b->finished) {
+        snprintf(g_err, sizeof(g_err), "%s: the batch is finished (lamehip_batch_reset starts it over)", who);
+        return -1;
+    }
+    if (batch_refuse_gain(b, who))
+        return -1;
+    if (stride != 1 && stride != 2) {
+        snprintf(g_err, sizeof(g_err), "%s: stride %d (1: planar, 2: interleaved)", who, stride);
+        return -1;
+    }
+    if (batch_incremental_check(b, who, 1) != 0)
+        return -1;
+    if ((rc = batch_stage_reserve(b)) != 0 || (rc = batch_append_reserve(b)) != 0)
+        return rc;
+    return batch_incremental_begin(b, who, 1);
+}
+
+static int
+batch_append_fits(const lamehip_batch * b, const char *who, int s, long long n)
+{
+    if (b->fed[(size_t) s] + b->staged[(size_t) s] + n <= b->cap)
+        return 1;
+    snprintf(g_err, sizeof(g_err), "%s: stream %d would exceed the batch's capacity of %ld samples", who, s, b->cap);
+    return 0;
+}
+
+/* Host buffers in the batch's element type, l and r `stride' elements from sample to sample as for lamehip_batch_set_input:
+ * staged in the pinned arena like the shorts of lamehip_batch_append -- 16-byte aligned, an interleaved chunk as it is --,
+ * on their way to HBM with the next lamehip_batch_encode_available / _finish, or earlier when the arena or the table is full. */
+extern "C" int
+lamehip_batch_append_input(lamehip_batch * b, int s, const void *l, const void *r, int stride, int n)
+{
+    static const char who[] = "lamehip_batch_append_input";
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int     rc;
+    if (!b || s < 0 || s >= b->B || n < 0 || (n > 0 && !l)) {
+        snprintf(g_err, sizeof(g_err), "%s: no such stream, a negative length or no samples", who);
+        return -1;
+    }
+    if ((rc = batch_append_enter(b, who, stride)) != 0)
+        return rc;
+    if (n == 0)
+        return 0;
+    bool const one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
+    if (one_plane)
+        r = l;                  /* mono: the second plane mirrors the first, the kernel never reads it */
+    if (!r) {
+        snprintf(g_err, sizeof(g_err), "%s: no right samples", who);
+        return -1;
+    }
+    if (!batch_append_fits(b, who, s, n))
+        return -1;
+    long const esz = b->esz;
+    bool const inter = (stride == 2 && !one_plane && (const char *) r == (const char *) l + esz);
+    /* pieces of at most a quarter of the arena's bytes per plane; when the arena or the table is full, what is staged
+     * leaves for HBM */
+    while (n > 0) {
+        long const piece_max = b->stage_cap / 2 / esz;
+        int const piece = (long) n > piece_max ? (int) piece_max : n;
+        long const plane = ((long) piece * esz + 15) & ~15L;    /* bytes */
+        long const need = (inter ? ((2L * piece * esz + 15) & ~15L) : (one_plane ? plane : 2 * plane)) / 2;     /* shorts */
+        long    at = (b->stage_used + 7) & ~7L;
+        if (at + need > b->stage_cap || b->ap_nseg == LH_STAGE_SEGS) {
+            if ((rc = batch_stage_flush(b, 1)) != 0)
+                return rc;
+            at = 0;
+        }
+        unsigned char *const dst = b->h_stage.get() + b->stage_arena_at + at * 2;
+        unsigned long long const dev = (unsigned long long) (uintptr_t) (b->d_stage.get() + b->stage_arena_at) + (unsigned long long) at * 2;
+        LhApSeg & g = b->h_ap.get()[b->ap_nseg];
+        g.at = b->fed[(size_t) s] + b->staged[(size_t) s];
+        g.n = piece;
+        g.stream = s;
+        g.l = dev;
+        if (inter) {
+            memcpy(dst, l, 2 * (size_t) piece * (size_t) esz);
+            g.r = dev + (unsigned long long) esz;
+            g.stride = 2;
+        }
+        else {
+            lh_pcm_copy_plane(dst, l, (int) esz, stride, piece);
+            if (!one_plane)
+                lh_pcm_copy_plane(dst + plane, r, (int) esz, stride, piece);
+            g.r = one_plane ? dev : dev + (unsigned long long) plane;
+            g.stride = 1;
+        }
+        b->stage_used = at + need;
+        b->ap_nseg++;
+        if (piece > b->ap_max_n)
+            b->ap_max_n = piece;
+        b->staged[(size_t) s] += piece;
+        l = (const char *) l + (size_t) piece * (size_t) stride * (size_t) esz;
+        r = (const char *) r + (size_t) piece * (size_t) stride * (size_t) esz;
+        n -= piece;
+    }
+    return 0;
+}
+
+/* the nsegs entries behind the staged ones in the pinned table (device addresses): one copy of the table, one launch, and
+ * the wait for it -- the samples are in the pool and counted on return */
+static int
+batch_append_resident(lamehip_batch * b, int nsegs, long long max_n)
+{
+    LhApSeg *const h = b->h_ap.get() + LH_STAGE_SEGS, *const d = b->d_ap.get() + LH_STAGE_SEGS;
+    int     rc;
+    if (nsegs <= 0)
+        return 0;
+    HIPCHK(hipMemcpyAsync(d, h, (size_t) nsegs * sizeof(LhApSeg), hipMemcpyHostToDevice, b->stream));
+    if ((rc = batch_append_launch(b, d, nsegs, max_n)) != 0)
+        return rc;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    batch_append_time(b);
+    for (int i = 0; i < nsegs; i++)
+        b->fed[(size_t) h[i].stream] += (long) h[i].n;
+    return 0;
+}
+
+/* the same from buffers in HBM, synchronous like lamehip_batch_set_input_device: whatever produced the buffers must have
+ * finished, and the caller may reuse them when the call returns */
+extern "C" int
+lamehip_batch_append_input_device(lamehip_batch * b, int s, const void *dl, const void *dr, int stride, int n)
+{
+    static const char who[] = "lamehip_batch_append_input_device";
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int     rc;
+    if (!b || s < 0 || s >= b->B || n < 0 || (n > 0 && !dl)) {
+        snprintf(g_err, sizeof(g_err), "%s: no such stream, a negative length or no samples", who);
+        return -1;
+    }
+    if ((rc = batch_append_enter(b, who, stride)) != 0)
+        return rc;
+    if (n == 0)
+        return 0;
+    if (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f)
+        dr = dl;
+    if (!dr) {
+        snprintf(g_err, sizeof(g_err), "%s: no right samples", who);
+        return -1;
+    }
+    if (!batch_append_fits(b, who, s, n))
+        return -1;
+    LhApSeg & g = b->h_ap.get()[LH_STAGE_SEGS];
+    g.l = (unsigned long long) (uintptr_t) dl;
+    g.r = (unsigned long long) (uintptr_t) dr;
+    g.at = b->fed[(size_t) s] + b->staged[(size_t) s];
+    g.n = n;
+    g.stream = s;
+    g.stride = stride;
+    return batch_append_resident(b, 1, n);
+}
+
+/* One round for all streams from one device array (a producer's [B, C, T] tensor): stream s takes nsamples[s] samples, the
+ * left ones from element s * stream_stride of `dev' on, the right ones plane_stride elements further on, `stride' elements
+ * from sample to sample.  ONE launch for the whole batch; synchronous as above. */
+extern "C" int
+lamehip_batch_append_device(lamehip_batch * b, const void *dev, long long stream_stride, long long plane_stride, int stride,
+                            const int *nsamples)
+{
+    static const char who[] = "lamehip_batch_append_device";
+    LhDeviceScope const on_device(b ? b->device : -1);
+    long long max_n = 0;
+    int     rc, nsegs = 0;
+    if (!b || !nsamples) {
+        snprintf(g_err, sizeof(g_err), "%s: no batch or no lengths", who);
+        return -1;
+    }
+    if ((rc = batch_append_enter(b, who, stride)) != 0)
+        return rc;
+    /* every stream checked before the first is counted: a refused round leaves the batch as it was */
+    for (int s = 0; s < b->B; s++) {
+        if (nsamples[s] < 0 || (nsamples[s] > 0 && !dev)) {
+            snprintf(g_err, sizeof(g_err), "%s: stream %d: a negative length or no samples", who, s);
+            return -1;
+        }
+        if (!batch_append_fits(b, who, s, nsamples[s]))
+            return -1;
+    }
+    bool const one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
+    for (int s = 0; s < b->B; s++) {
+        if (nsamples[s] == 0)
+            continue;
+        LhApSeg & g = b->h_ap.get()[LH_STAGE_SEGS + nsegs++];
+        g.l = (unsigned long long) ((uintptr_t) dev + (uintptr_t) ((long long) s * stream_stride * b->esz));
+        g.r = one_plane ? g.l : g.l + (unsigned long long) (plane_stride * b->esz);
+        g.at = b->fed[(size_t) s] + b->staged[(size_t) s];
+        g.n = nsamples[s];
+        g.stream = s;
+        g.stride = stride;
+        if (nsamples[s] > max_n)
+            max_n = nsamples[s];
+    }
+    return batch_append_resident(b, nsegs, max_n);
+}
+
+/* HIP-event time of the append launches (lh_append_kernel) since, and including, the last lamehip_batch_encode_available /
+ * _finish; not part of lamehip_batch_last_kernel_ms */
+extern "C" float
+lamehip_batch_last_append_ms(lamehip_batch * b)
+{
+    return b ? b->ap_ms : 0.0f;
 }
 
 /* frames of a stream that are complete once `fed' samples are in: frame f reads 1904 samples from
@@ -1118,18 +1439,23 @@ batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
         return rc;
     if (total == 0) {
         HIPCHK(hipStreamSynchronize(b->stream));
+        batch_append_time(b);
         return 0;
     }
     {
+        /* (a typed batch: the kernels read the float pool the appends filled) */
         LhLaunchPlan plan;
         if ((rc = batch_plan(b, descs, &plan)) != 0
-            || (rc = batch_launch(b, b->d_pcm.get(), (const float *) 0, (const LhStreamDesc *) b->d_stage.get(), plan, (uint8_t *) 0)) != 0)
+            || (rc = batch_launch(b, batch_reads_floats(b) ? (const int16_t *) 0 : b->d_pcm.get(),
+                                  batch_reads_floats(b) ? b->d_pcmf.get() : (const float *) 0, (const LhStreamDesc *) b->d_stage.get(), plan,
+                                  (uint8_t *) 0)) != 0)
             return rc;
     }
     b->launched = 1;
     b->h_new.resize((size_t) total);
     HIPCHK(hipMemcpyAsync(b->h_new.data(), b->d_out.get(), (size_t) total * sizeof(LhFrameOut), hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
+    batch_append_time(b);
     for (int s = 0; s < b->B; s++) {
         LhBitstream *bs = &b->packer[(size_t) s];
         std::vector < unsigned char >&out = b->pending[(size_t) s];
@@ -1168,10 +1494,12 @@ lamehip_batch_encode_available(lamehip_batch * b)
     }
     if (batch_refuse_gain(b, "lamehip_batch_encode_available"))
         return -1;
-    if ((rc = batch_incremental_begin(b)) != 0)
+    if ((rc = batch_incremental_begin(b, "lamehip_batch_encode_available", 0)) != 0)
         return rc;
     if ((rc = batch_stage_reserve(b)) != 0)
         return rc;
+    batch_append_time(b);
+    b->ap_ms = 0;               /* (lamehip_batch_last_append_ms counts from here) */
     upto.resize((size_t) b->B);
     for (int s = 0; s < b->B; s++)
         upto[(size_t) s] = frames_complete(b->fed[(size_t) s] + b->staged[(size_t) s], b->cfg);
@@ -1194,10 +1522,12 @@ lamehip_batch_finish(lamehip_batch * b)
     }
     if (batch_refuse_gain(b, "lamehip_batch_finish"))
         return -1;
-    if ((rc = batch_incremental_begin(b)) != 0)
+    if ((rc = batch_incremental_begin(b, "lamehip_batch_finish", 0)) != 0)
         return rc;
     if ((rc = batch_stage_reserve(b)) != 0)
         return rc;
+    batch_append_time(b);
+    b->ap_ms = 0;
     upto.resize((size_t) b->B);
     for (int s = 0; s < b->B; s++) {
         long const len = b->fed[(size_t) s] + b->staged[(size_t) s];
@@ -1267,6 +1597,8 @@ lamehip_batch_reset(lamehip_batch * b)
         b->have_last.assign((size_t) b->B, 0);
         b->stage_used = 0;
         b->stage_nseg = 0;
+        b->ap_nseg = 0;
+        b->ap_max_n = 0;
         b->finished = 0;
     }
     /* every gain is forgotten, and every stream with it: the next encode measures all of them again */
@@ -1994,7 +2326,8 @@ lamehip_batch_get_converted(lamehip_batch * b, int s, float *l, float *r, long c
         snprintf(g_err, sizeof(g_err), "lamehip_batch_get_converted: stream %d has not been converted yet (lamehip_batch_encode)", s);
         return -1;
     }
-    long const n = b->len[(size_t) s];
+    /* (an incremental typed batch: the float planes up to what has reached the pool) */
+    long const n = b->incremental ? b->fed[(size_t) s] : b->len[(size_t) s];
     if (n > cap)
         return -1;
     HIPCHK(hipStreamSynchronize(b->stream));

@@ -61,6 +61,19 @@ typedef struct LhInParams {
     long long cap;              /* row length of both pools */
 } LhInParams;
 
+/* A segment of an append launch (lh_ingest.hip): n samples of the batch's element type, the left ones from device
+ * address l on and the right ones from r on, `stride' elements from one sample to the next (1: planar; 2: interleaved,
+ * r = l + one element), go to positions [at, at + n) of rows `stream' -- of the float pool through the arithmetic above
+ * when the batch's type is int32 / float, of the s16 pool as they are when it is s16.  Nothing outside the segment's
+ * samples is read, nothing outside [at, at + n) is written; with one_plane set r is never read. */
+typedef struct LhApSeg {
+    unsigned long long l, r;
+    long long at;
+    long long n;
+    int     stream;
+    int     stride;
+} LhApSeg;
+
 #define LH_IN_NT 256            /* lanes of a workgroup */
 #define LH_IN_STEPS 4           /* quads of four positions per lane */
 #define LH_IN_QUADS (LH_IN_NT * LH_IN_STEPS)    /* quads per workgroup: 4096 positions of a stream */

@@ -96,18 +96,19 @@ def _is_device_array(x):
     return hasattr(x, "data_ptr") and bool(getattr(x, "is_cuda", False))
 
 
-def _check_input(x, dtype, what):
-    """x as the batch's set_input takes it -- a numpy array, or a device array, of exactly `dtype', C-contiguous: never cast"""
+def _check_input(x, dtype, what, who="set_input"):
+    """x as the batch's set_input / append_input takes it -- a numpy array, or a device array, of exactly `dtype',
+    C-contiguous: never cast"""
     if _is_device_array(x):
         name = str(x.dtype).split(".")[-1]
         if name != dtype.name:
-            raise TypeError("set_input: %s is %s, the batch's sample type takes %s" % (what, name, dtype.name))
+            raise TypeError("%s: %s is %s, the batch's sample type takes %s" % (who, what, name, dtype.name))
         if not x.is_contiguous():
-            raise ValueError("set_input: %s is not contiguous" % what)
+            raise ValueError("%s: %s is not contiguous" % (who, what))
         return x
     x = np.asarray(x)
     if x.dtype != dtype:
-        raise TypeError("set_input: %s is %s, the batch's sample type takes %s" % (what, x.dtype.name, dtype.name))
+        raise TypeError("%s: %s is %s, the batch's sample type takes %s" % (who, what, x.dtype.name, dtype.name))
     return np.ascontiguousarray(x)
 
 
@@ -225,30 +226,36 @@ class Batch:
         array [n, 2] (as `interleaved', or as a two-dimensional `left').  numpy arrays go through the pinned mirror; arrays
         that live on the batch's GPU (anything with data_ptr() and is_cuda, such as a torch tensor) are copied on the
         device -- whatever produced them must have finished.  The dtype must be the batch's: nothing is cast."""
+        ptrs, stride, n, on_device, keep = self._input_args("set_input", left, right, interleaved)
+        fn = self.lib.lamehip_batch_set_input_device if on_device else self.lib.lamehip_batch_set_input
+        rc = fn(self.b, s, ptrs[0], ptrs[1], stride, n)
+        if rc:
+            raise RuntimeError("lamehip_batch_set_input failed (%d): %s" % (rc, last_error()))
+
+    def _input_args(self, who, left, right, interleaved):
+        """what set_input / append_input hand to the library: (left pointer, right pointer), stride, samples, whether the
+        arrays live on the device, and the arrays themselves (to be kept alive across the call)"""
         dtype = PCM_DTYPES[self.sample_type]
         if interleaved is None and left is not None and right is None and len(getattr(left, "shape", ())) == 2:
             interleaved, left = left, None
         if interleaved is not None:
             if left is not None or right is not None:
-                raise ValueError("set_input: planar arrays or an interleaved one, not both")
-            x = _check_input(interleaved, dtype, "interleaved")
+                raise ValueError("%s: planar arrays or an interleaved one, not both" % who)
+            x = _check_input(interleaved, dtype, "interleaved", who)
             if len(x.shape) != 2 or x.shape[1] != 2:
-                raise ValueError("set_input: an interleaved array is [n, 2]")
+                raise ValueError("%s: an interleaved array is [n, 2]" % who)
             n, stride = int(x.shape[0]), 2
             base = x.data_ptr() if _is_device_array(x) else x.ctypes.data
             ptrs, keep = (base, base + dtype.itemsize), (x,)
         else:
-            l = _check_input(left, dtype, "left")
-            r = l if right is None else _check_input(right, dtype, "right")     # mono: not read
+            l = _check_input(left, dtype, "left", who)
+            r = l if right is None else _check_input(right, dtype, "right", who)        # mono: not read
             if len(l.shape) != 1 or tuple(r.shape) != tuple(l.shape) or _is_device_array(l) != _is_device_array(r):
-                raise ValueError("set_input: planar input is two one-dimensional arrays of one length, in one place")
+                raise ValueError("%s: planar input is two one-dimensional arrays of one length, in one place" % who)
             n, stride = int(l.shape[0]), 1
             ptrs = (l.data_ptr(), r.data_ptr()) if _is_device_array(l) else (l.ctypes.data, r.ctypes.data)
             keep = (l, r)
-        fn = self.lib.lamehip_batch_set_input_device if _is_device_array(keep[0]) else self.lib.lamehip_batch_set_input
-        rc = fn(self.b, s, ptrs[0], ptrs[1], stride, n)
-        if rc:
-            raise RuntimeError("lamehip_batch_set_input failed (%d): %s" % (rc, last_error()))
+        return ptrs, stride, n, _is_device_array(keep[0]), keep
 
     def input_host(self):
         """The pinned host mirror of the input pool in the batch's sample type, [streams, 2, capacity] (no copy): fill it,
@@ -322,6 +329,58 @@ class Batch:
         if rc:
             raise RuntimeError("lamehip_batch_append failed (%d): %s" % (rc, last_error()))
 
+    def append_input(self, s, left=None, right=None, interleaved=None):
+        """More samples of stream s in the batch's sample type (any number, also 0), arguments as for set_input: planar
+        `left' / `right' (right=None: mono) or one interleaved array [n, 2]; the dtype must be the batch's, nothing is
+        cast.  numpy arrays are staged like append()'s shorts and leave with the next encode_available() / finish();
+        arrays on the batch's GPU (data_ptr() and is_cuda, such as torch tensors) are in the pool when the call returns --
+        whatever produced them must have finished.  The two may be mixed, and on a PCM_S16 batch with append()."""
+        ptrs, stride, n, on_device, keep = self._input_args("append_input", left, right, interleaved)
+        fn = self.lib.lamehip_batch_append_input_device if on_device else self.lib.lamehip_batch_append_input
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        rc = fn(self.b, s, ptrs[0], ptrs[1], stride, n)
+        if rc:
+            raise RuntimeError("lamehip_batch_append_input failed (%d): %s" % (rc, last_error()))
+
+    def append_device(self, x, lengths):
+        """One round for all streams from one array on the batch's GPU, with ONE launch: x is [B, 2, T] (planes), [B, T, 2]
+        (interleaved) or, on a mono batch, [B, T]; stream s takes its first lengths[s] samples (ragged, 0 allowed).  The
+        strides are the array's own (a slice x[:, :, a:b] of a larger tensor is fine), samples lie next to each other.
+        Whatever produced x must have finished; it may be reused when the call returns."""
+        dtype = PCM_DTYPES[self.sample_type]
+        if not _is_device_array(x):
+            raise TypeError("append_device: takes a device array (data_ptr() and is_cuda), append_input takes host arrays")
+        name = str(x.dtype).split(".")[-1]
+        if name != dtype.name:
+            raise TypeError("append_device: the array is %s, the batch's sample type takes %s" % (name, dtype.name))
+        shape, st = tuple(int(v) for v in x.shape), tuple(int(v) for v in x.stride())
+        if len(shape) == 3 and shape[0] == self.n and shape[1] == 2:
+            total, args = shape[2], (st[0], st[1], st[2])
+        elif len(shape) == 3 and shape[0] == self.n and shape[2] == 2:
+            total, args = shape[1], (st[0], st[2], st[1])
+        elif len(shape) == 2 and shape[0] == self.n and self.enc.channels == 1:
+            total, args = shape[1], (st[0], 0, st[1])
+        else:
+            raise ValueError("append_device: the array is [streams, 2, T], [streams, T, 2] or, on a mono batch, [streams, T]")
+        if total <= 1:
+            args = (args[0], args[1], 2 if args[1] == 1 else 1)         # (no second sample: its distance means nothing)
+        if args[2] not in (1, 2) or (args[2] == 2 and args[1] != 1):
+            raise ValueError("append_device: samples lie next to each other, or interleaved with the other plane's")
+        lengths = [int(v) for v in lengths]
+        if len(lengths) != self.n or min(lengths) < 0 or max(lengths) > total:
+            raise ValueError("append_device: one length per stream, between 0 and what the array holds")
+        n = (C.c_int * self.n)(*lengths)
+        self.lib.lamehip_batch_append_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p]
+        rc = self.lib.lamehip_batch_append_device(self.b, x.data_ptr(), args[0], args[1], args[2], n)
+        if rc:
+            raise RuntimeError("lamehip_batch_append_device failed (%d): %s" % (rc, last_error()))
+
+    def append_ms(self):
+        """HIP-event time of the append launches since, and including, the last encode_available() / finish()."""
+        self.lib.lamehip_batch_last_append_ms.restype = C.c_float
+        self.lib.lamehip_batch_last_append_ms.argtypes = [C.c_void_p]
+        return float(self.lib.lamehip_batch_last_append_ms(self.b))
+
     def encode_available(self):
         """Encode every stream's newly complete frames (one launch); returns how many there were."""
         self.lib.lamehip_batch_encode_available.argtypes = [C.c_void_p]
@@ -371,7 +430,7 @@ class Batch:
         """The converted signal of stream s as the encoder reads it: float32 [2, converted length] (test accessor)."""
         self.lib.lamehip_batch_get_converted.restype = C.c_long
         self.lib.lamehip_batch_get_converted.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
-        cap = (self.frames(s) + 4) * 1152
+        cap = max((self.frames(s) + 4) * 1152, self.capacity)    # (an incremental batch knows its frames at finish())
         out = np.zeros((2, cap), dtype=np.float32)
         n = self.lib.lamehip_batch_get_converted(self.b, s, out[0].ctypes.data, out[1].ctypes.data, cap)
         if n < 0:

@@ -253,8 +253,9 @@ int     lamehip_batch_set_length(lamehip_batch *, int stream, long nsamples);
 int     lamehip_batch_set_device_resampling(lamehip_batch *, int on);
 /* test accessor: the converted signal of a stream (float planes as the encoder reads them), valid after
  * lamehip_batch_set_pcm when the host converts and after lamehip_batch_encode when the device does -- also the float
- * planes of a batch of another sample type that does not convert, after lamehip_batch_encode --; waits for the
- * batch's stream.  Returns the converted length, or a negative code (-1 also when it exceeds cap). */
+ * planes of a batch of another sample type that does not convert, after lamehip_batch_encode, or, on an incremental
+ * batch of such a type, up to what has reached the pool (device-resident appends at once, staged ones with the next
+ * lamehip_batch_encode_available / _finish) --; waits for the batch's stream.  Returns the converted length, or a negative code (-1 also when it exceeds cap). */
 long    lamehip_batch_get_converted(lamehip_batch *, int stream, float *l, float *r, long cap);
 /* HIP-event time in ms of the device conversion of the last lamehip_batch_encode (after lamehip_batch_sync); 0 when
  * none ran.  It is not part of lamehip_batch_last_kernel_ms / _parts_ms. */
@@ -333,6 +334,39 @@ int     lamehip_batch_append(lamehip_batch *, int stream, const short *l, const 
 int     lamehip_batch_encode_available(lamehip_batch *);
 int     lamehip_batch_drain(lamehip_batch *, int stream, unsigned char *out, int out_size);
 int     lamehip_batch_finish(lamehip_batch *);
+/* Appends in the batch's own element type (lamehip_batch_set_sample_type; an s16 batch too), from host memory or from
+ * HBM.  On an int32 / float batch a chunk goes through lame_copy_inbuffer's arithmetic straight into the float pool the
+ * kernels read (one kernel, csrc/lh_ingest.hip: lh_append_kernel): each call is the reference entry point the type is
+ * named after, and lamehip_batch_drain hands over the bytes that call would have returned.  On an s16 batch it is
+ * lame_encode_buffer or, with stride 2, lame_encode_buffer_interleaved, and may be mixed with lamehip_batch_append.
+ * The first call switches the batch to incremental use whatever its sample type; capacity, lamehip_batch_finish /
+ * lamehip_batch_reset and lamehip_batch_drain are as above.  lamehip_batch_append (shorts) stays refused on a batch of
+ * another type.  -1, with a lamehip_last_error() that names the call: a stream that would exceed the capacity, a stride
+ * other than 1 or 2, a finished batch, a batch that converts the sample rate, packs on the device or measures ReplayGain
+ * (the conversion plan and the gain plan depend on how the reference is called chunk by chunk: not built yet).
+ * LAMEHIP_ERR_DEVICE when an allocation fails, the batch is then as it was.
+ *   lamehip_batch_append_input         host buffers, l and r `stride' elements from sample to sample as for
+ *                                      lamehip_batch_set_input; staged in the pinned arena like the shorts of
+ *                                      lamehip_batch_append (16 MB: 4-byte elements halve the samples it holds), on their
+ *                                      way to HBM with the next lamehip_batch_encode_available / _finish: one copy of the
+ *                                      table, one of the bytes in use, one launch
+ *   lamehip_batch_append_input_device  the same from buffers in HBM, synchronous like lamehip_batch_set_input_device:
+ *                                      whatever produced the buffers must have finished, the call makes one launch on the
+ *                                      batch's stream and returns once the samples are in the pool -- the caller may reuse
+ *                                      the buffers at once
+ *   lamehip_batch_append_device        one round for ALL streams from one device array, such as a producer's
+ *                                      [B, C, T_chunk] tensor: stream s takes nsamples[s] samples (ragged, 0 allowed), the
+ *                                      left ones from element s * stream_stride of `dev' on, the right ones plane_stride
+ *                                      elements further on; ONE launch for the whole batch, synchronous as above
+ * A chunk's place in its stream is fixed when it is appended, so staged and device-resident appends of one stream may
+ * follow each other in any order. */
+int     lamehip_batch_append_input(lamehip_batch *, int stream, const void *l, const void *r, int stride, int nsamples);
+int     lamehip_batch_append_input_device(lamehip_batch *, int stream, const void *dev_l, const void *dev_r, int stride, int nsamples);
+int     lamehip_batch_append_device(lamehip_batch *, const void *dev, long long stream_stride, long long plane_stride, int stride,
+                                    const int *nsamples);
+/* HIP-event time in ms of the append launches since, and including, the last lamehip_batch_encode_available / _finish; not
+ * part of lamehip_batch_last_kernel_ms / _parts_ms, like lamehip_batch_last_ingest_ms */
+float   lamehip_batch_last_append_ms(lamehip_batch *);
 /* encode every stream completely (all frames incl. the flush frames), payload
  * stays in HBM; asynchronous on the batch's HIP stream */
 int     lamehip_batch_encode(lamehip_batch *);
