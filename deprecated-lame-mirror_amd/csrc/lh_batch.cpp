@@ -19,6 +19,9 @@ extern "C" int lh_launch_resample_typed(int type, const LhRsParams * p, const fl
 extern "C" int lh_launch_ingest(int type, const LhInParams * p, const LhInStream * streams, int nstreams, long long max_n, const void *in,
                                 float *out, void *stream);
 extern "C" int lh_launch_append(int type, const LhInParams * p, const LhApSeg * segs, int nsegs, long long max_n, void *pool, void *stream);
+extern "C" int lh_launch_append_raw(int esz, const LhInParams * p, const LhApSeg * segs, int nsegs, long long max_n, void *pool, void *stream);
+extern "C" int lh_launch_resample_tiles(int type, const LhRsParams * p, const float *bank, const LhRsTile * tiles, long long ntiles,
+                                        const long long *lens, const void *pcm, float *pcmf, void *stream);
 extern "C" int lh_launch_deinterleave(int esz, const void *src_l, const void *src_r, void *dst_l, void *dst_r, long long n, void *stream);
 extern "C" int lh_launch_gain(int floats, const LhGainParams * p, const LhGainStream * streams, int nstreams, const int *trunk, const int *tails,
                               const void *pool, double *pairs, void *stream);
@@ -118,6 +121,20 @@ struct lamehip_batch {
     LhEvent ev_rs[2];
     int     rs_ran = 0;         /* the last lamehip_batch_encode converted something (between ev_rs[0] and ev_rs[1]) */
     float   rs_ms = 0;
+    /* ... or, after lamehip_batch_set_incremental_resampling on top of that, round by round: the appends put their chunks
+     * into the input pool as they are and plan their calls at once (lh_rs_plan_call from the stream's cursor, cut into
+     * tiles), lamehip_batch_encode_available / _finish run ONE launch of lh_resample_tiles_kernel over the tiles planned
+     * since the last round, between the append launches and the encode launch -- a chunk's first outputs reach back into
+     * the chunk before, which may still be in the staging arena when the append returns */
+    int     inc_rs = 0;
+    long    inc_capf = 0;       /* converted samples per stream the appends allow: capf (less under LAMEHIP_INC_RS_ROOM) */
+    std::vector < LhRsCursor > rs_cur;  /* per stream: the converter behind the calls so far */
+    std::vector < long long >rs_conv;   /* per stream: converted samples the rounds so far have put into the float pool */
+    std::vector < LhRsBlock > rs_blk;   /* the blocks of the call being planned */
+    std::vector < LhRsTile > h_tiles;   /* the round's tiles */
+    std::vector < long long >h_rs_lens; /* input samples per stream, as the round's launch sees them */
+    LhDevBuf < LhRsTile > d_tiles;
+    LhDevBuf < long long >d_rs_lens;
     /* ReplayGain (lamehip_batch_set_replaygain): lamehip_batch_encode measures the radio gain of the streams declared since
      * their last analysis with lh_gain.hip, behind the conversion / ingest kernels and in front of the analysis kernels.  The
      * host plans (lh_gain_plan: the blocks the handle API would hand to lh_rg_block), the kernel leaves every stream's window
@@ -963,10 +980,12 @@ batch_incremental_check(const lamehip_batch * b, const char *who, int typed_ok)
         return -1;
     }
     /* (how the reference converts the rate depends on how it is called, chunk by chunk: the conversion plan of a batch is
-     * made for whole streams) */
-    if (b->rate_in || b->dev_pack) {
+     * made for whole streams, unless lamehip_batch_set_incremental_resampling asked for the plan that follows the calls) */
+    if ((b->rate_in && !b->inc_rs) || b->dev_pack) {
         snprintf(g_err, sizeof(g_err), "%s: incremental batches take the encoder's own input rate and the host packer, this batch %s", who,
-                 b->rate_in ? "converts the sample rate" : "packs on the device (lamehip_batch_set_device_packing)");
+                 !b->rate_in || b->inc_rs ? "packs on the device (lamehip_batch_set_device_packing)"
+                 : b->dev_rs ? "converts the sample rate (lamehip_batch_set_incremental_resampling lets it do so round by round)"
+                 : "converts the sample rate");
         return -1;
     }
     return 0;
@@ -1086,8 +1105,10 @@ batch_append_launch(lamehip_batch * b, const LhApSeg * segs, int nsegs, long lon
     p.one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
     p.cap = b->cap;
     HIPCHK(hipEventRecord(b->ev_ap[0], b->stream));
-    int const rc = lh_launch_append(b->stype, &p, segs, nsegs, max_n,
-                                    b->stype == LH_PCM_S16 ? (void *) b->d_pcm.get() : (void *) b->d_pcmf.get(), (void *) (hipStream_t) b->stream);
+    /* (a batch that converts round by round: into the input pool as they are, the converter reads them there) */
+    int const rc = b->inc_rs ? lh_launch_append_raw(b->esz, &p, segs, nsegs, max_n, (void *) b->d_pcm.get(), (void *) (hipStream_t) b->stream)
+        : lh_launch_append(b->stype, &p, segs, nsegs, max_n,
+                           b->stype == LH_PCM_S16 ? (void *) b->d_pcm.get() : (void *) b->d_pcmf.get(), (void *) (hipStream_t) b->stream);
     if (rc)
         return set_err("append launch", (hipError_t) rc);
     HIPCHK(hipEventRecord(b->ev_ap[1], b->stream));
@@ -1133,6 +1154,56 @@ batch_stage_flush(lamehip_batch * b, int wait)
     return 0;
 }
 
+/* A batch that converts round by round: the append of n samples to stream s is one lame_encode_buffer call to the converter,
+ * planned here from the stream's cursor.  Refused (-1, `who' in the message) when the stream, flushed right after this call,
+ * would not fit its rows of the float pool -- so lamehip_batch_finish never lacks room.  commit: the cursor advances and the
+ * call's tiles join the round's list; else the call is only checked, and *ntiles (when given) grows by its tiles.  An
+ * allocation failure returns LAMEHIP_ERR_DEVICE; either way a call that does not return 0 leaves the batch as it was. */
+static int
+batch_rs_plan_append(lamehip_batch * b, const char *who, int s, int n, bool commit, size_t *ntiles = nullptr)
+{
+    int const fs = fs_of(b->cfg), mfn = mfn_of(b->cfg);
+    LhRsCursor c = b->rs_cur[(size_t) s], end;
+    int     padding = 0;
+    size_t  nt = 0;
+    int const nblk = lh_rs_plan_call(b->rs, fs, mfn, &c, n, nullptr, 0);
+    try {
+        b->rs_blk.resize((size_t) nblk);
+    }
+    catch(const std::bad_alloc &) {
+        snprintf(g_err, sizeof(g_err), "%s: out of memory (conversion plan)", who);
+        return LAMEHIP_ERR_DEVICE;
+    }
+    c = b->rs_cur[(size_t) s];
+    (void) lh_rs_plan_call(b->rs, fs, mfn, &c, n, b->rs_blk.data(), nblk);
+    end = c;
+    (void) lh_rs_plan_flush(b->rs, fs, mfn, &end, nullptr, 0, &padding);
+    if (end.fed > (long long) b->inc_capf) {
+        snprintf(g_err, sizeof(g_err), "%s: stream %d, flushed behind this call, would be %lld converted samples: more than the float pool's "
+                 "%ld per stream", who, s, end.fed, b->inc_capf);
+        return -1;
+    }
+    for (const LhRsBlock & k:b->rs_blk)
+        nt += (size_t) lh_rs_block_tiles(b->rs, &k, s, nullptr, 0);
+    if (ntiles)
+        *ntiles += nt;
+    if (!commit)
+        return 0;
+    size_t const at = b->h_tiles.size();
+    try {
+        b->h_tiles.resize(at + nt);
+    }
+    catch(const std::bad_alloc &) {
+        snprintf(g_err, sizeof(g_err), "%s: out of memory (tile table)", who);
+        return LAMEHIP_ERR_DEVICE;
+    }
+    nt = at;
+    for (const LhRsBlock & k:b->rs_blk)
+        nt += (size_t) lh_rs_block_tiles(b->rs, &k, s, b->h_tiles.data() + nt, (int) (b->h_tiles.size() - nt));
+    b->rs_cur[(size_t) s] = c;
+    return 0;
+}
+
 extern "C" int
 lamehip_batch_append(lamehip_batch * b, int s, const short *l, const short *r, int n)
 {
@@ -1163,6 +1234,8 @@ lamehip_batch_append(lamehip_batch * b, int s, const short *l, const short *r, i
         return -1;
     }
     if ((rc = batch_stage_reserve(b)) != 0)
+        return rc;
+    if (b->inc_rs && (rc = batch_rs_plan_append(b, "lamehip_batch_append", s, n, true)) != 0)
         return rc;
     /* pieces of at most half the arena; when the arena or the chunk table is full, what is staged leaves for HBM */
     while (n > 0) {
@@ -1251,6 +1324,8 @@ lamehip_batch_append_input(lamehip_batch * b, int s, const void *l, const void *
     }
     if (!batch_append_fits(b, who, s, n))
         return -1;
+    if (b->inc_rs && (rc = batch_rs_plan_append(b, who, s, n, true)) != 0)
+        return rc;
     long const esz = b->esz;
     bool const inter = (stride == 2 && !one_plane && (const char *) r == (const char *) l + esz);
     /* pieces of at most a quarter of the arena's bytes per plane; when the arena or the table is full, what is staged
@@ -1340,6 +1415,8 @@ lamehip_batch_append_input_device(lamehip_batch * b, int s, const void *dl, cons
     }
     if (!batch_append_fits(b, who, s, n))
         return -1;
+    if (b->inc_rs && (rc = batch_rs_plan_append(b, who, s, n, true)) != 0)
+        return rc;
     LhApSeg & g = b->h_ap.get()[LH_STAGE_SEGS];
     g.l = (unsigned long long) (uintptr_t) dl;
     g.r = (unsigned long long) (uintptr_t) dr;
@@ -1376,6 +1453,23 @@ lamehip_batch_append_device(lamehip_batch * b, const void *dev, long long stream
         if (!batch_append_fits(b, who, s, nsamples[s]))
             return -1;
     }
+    if (b->inc_rs) {
+        /* (the same for the conversion: every stream's call checked and the round's list made large enough, then counted) */
+        size_t  ntiles = 0;
+        for (int s = 0; s < b->B; s++)
+            if (nsamples[s] > 0 && (rc = batch_rs_plan_append(b, who, s, nsamples[s], false, &ntiles)) != 0)
+                return rc;
+        try {
+            b->h_tiles.reserve(b->h_tiles.size() + ntiles);
+        }
+        catch(const std::bad_alloc &) {
+            snprintf(g_err, sizeof(g_err), "%s: out of memory (tile table)", who);
+            return LAMEHIP_ERR_DEVICE;
+        }
+        for (int s = 0; s < b->B; s++)
+            if (nsamples[s] > 0 && (rc = batch_rs_plan_append(b, who, s, nsamples[s], true)) != 0)
+                return rc;
+    }
     bool const one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
     for (int s = 0; s < b->B; s++) {
         if (nsamples[s] == 0)
@@ -1410,6 +1504,59 @@ frames_complete(long fed, const LhConfig & c)
     return have >= mfn_of(c) ? (int) ((have - mfn_of(c)) / fs_of(c) + 1) : 0;
 }
 
+/* A batch that converts round by round: the tiles planned since the last round (lh_resample_tiles_kernel), ONE launch on
+ * the batch's stream between ev_rs[0] and ev_rs[1], behind the append launches -- every chunk is in the input pool and
+ * counted in fed[] -- and in front of the encode launch.  The list stays until the round's wait: it is read from here. */
+static int
+batch_tiles_launch(lamehip_batch * b)
+{
+    size_t const ntiles = b->h_tiles.size();
+    b->rs_ran = 0;
+    if (ntiles == 0)
+        return 0;
+    for (int s = 0; s < b->B; s++)
+        b->h_rs_lens[(size_t) s] = b->fed[(size_t) s];
+    /* (twice what is needed; drained first: nothing of an earlier round is in flight, a round ends with a wait) */
+    HIPCHK(b->d_tiles.reserve(ntiles, ntiles + 1024, b->stream));
+    HIPCHK(hipMemcpyAsync(b->d_tiles.get(), b->h_tiles.data(), ntiles * sizeof(LhRsTile), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemcpyAsync(b->d_rs_lens.get(), b->h_rs_lens.data(), (size_t) b->B * sizeof(long long), hipMemcpyHostToDevice, b->stream));
+    LhRsParams p;
+    memset(&p, 0, sizeof(p));
+    p.ratio = b->rs->ratio;
+    p.m = b->stype != LH_PCM_S16 ? lh_pcm_matrix(b->stype, b->cfg.pcm_scale, b->cfg.pcm_mix, b->cfg.pcm_scale_r)
+        : lh_rs_matrix(b->cfg.pcm_scale, b->cfg.pcm_mix, b->cfg.pcm_scale_r);
+    p.taps = b->rs->taps;
+    p.phases = b->rs->phases;
+    p.channels = b->cfg.channels;
+    p.one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
+    p.cap_in = b->cap;
+    p.cap_out = b->capf;
+    HIPCHK(hipEventRecord(b->ev_rs[0], b->stream));
+    int const rc = lh_launch_resample_tiles(b->stype, &p, b->d_rs_bank.get(), b->d_tiles.get(), (long long) ntiles, b->d_rs_lens.get(),
+                                            b->d_pcm.get(), b->d_pcmf.get(), (void *) (hipStream_t) b->stream);
+    if (rc)
+        return set_err("conversion launch", (hipError_t) rc);
+    HIPCHK(hipEventRecord(b->ev_rs[1], b->stream));
+    b->rs_ran = 1;
+    return 0;
+}
+
+/* behind the round's wait: the time of its tile launch (lamehip_batch_last_resample_ms), and the list is done with */
+static void
+batch_tiles_done(lamehip_batch * b)
+{
+    if (!b->inc_rs)
+        return;
+    b->rs_ms = 0;
+    if (b->rs_ran && hipEventElapsedTime(&b->rs_ms, b->ev_rs[0], b->ev_rs[1]) != hipSuccess) {
+        (void) hipGetLastError();
+        b->rs_ms = 0;
+    }
+    b->h_tiles.clear();
+    for (int s = 0; s < b->B; s++)
+        b->rs_conv[(size_t) s] = b->rs_cur[(size_t) s].fed;
+}
+
 /* encode frames [done, upto[s]) of every stream and pack them into pending[]; `end' marks the
  * streams' last frames (flush) */
 static int
@@ -1418,14 +1565,16 @@ batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
     LhStreamDesc *descs = (LhStreamDesc *) b->h_stage.get();
     long long total = 0;
     int     rc;
+    /* (a batch that converts: the kernels read the float pool's rows, as far as the conversion has come) */
+    long long const row = b->inc_rs ? b->capf : b->cap;
     for (int s = 0; s < b->B; s++) {
         LhStreamDesc & d = descs[s];
         int const nf = upto[(size_t) s] - b->done[(size_t) s];
         memset(&d, 0, sizeof(d));
-        d.pcm_l = ((long long) s * 2) * b->cap;
-        d.pcm_r = ((long long) s * 2 + 1) * b->cap;
+        d.pcm_l = ((long long) s * 2) * row;
+        d.pcm_r = ((long long) s * 2 + 1) * row;
         d.pcm_base = 0;
-        d.nsamples = b->fed[(size_t) s] + b->staged[(size_t) s];
+        d.nsamples = b->inc_rs ? (long) b->rs_cur[(size_t) s].fed : b->fed[(size_t) s] + b->staged[(size_t) s];
         d.out_index = total;
         d.frame_begin = b->done[(size_t) s];
         d.frame_end = upto[(size_t) s];
@@ -1437,9 +1586,13 @@ batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
     HIPCHK(hipMemcpyAsync(b->d_stage.get(), b->h_stage.get(), (size_t) b->B * sizeof(LhStreamDesc), hipMemcpyHostToDevice, b->stream));
     if ((rc = batch_stage_flush(b, 0)) != 0)
         return rc;
+    /* (the round's conversion, also when no frame is complete yet: the floats are there when one is) */
+    if (b->inc_rs && (rc = batch_tiles_launch(b)) != 0)
+        return rc;
     if (total == 0) {
         HIPCHK(hipStreamSynchronize(b->stream));
         batch_append_time(b);
+        batch_tiles_done(b);
         return 0;
     }
     {
@@ -1456,6 +1609,7 @@ batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
     HIPCHK(hipMemcpyAsync(b->h_new.data(), b->d_out.get(), (size_t) total * sizeof(LhFrameOut), hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     batch_append_time(b);
+    batch_tiles_done(b);
     for (int s = 0; s < b->B; s++) {
         LhBitstream *bs = &b->packer[(size_t) s];
         std::vector < unsigned char >&out = b->pending[(size_t) s];
@@ -1502,8 +1656,48 @@ lamehip_batch_encode_available(lamehip_batch * b)
     b->ap_ms = 0;               /* (lamehip_batch_last_append_ms counts from here) */
     upto.resize((size_t) b->B);
     for (int s = 0; s < b->B; s++)
-        upto[(size_t) s] = frames_complete(b->fed[(size_t) s] + b->staged[(size_t) s], b->cfg);
+        upto[(size_t) s] = frames_complete(b->inc_rs ? (long) b->rs_cur[(size_t) s].fed : b->fed[(size_t) s] + b->staged[(size_t) s], b->cfg);
     return batch_encode_range(b, upto, 0);
+}
+
+/* A batch that converts round by round, at its end: every stream's flush planned from its cursor (lh_rs_plan_flush) -- its
+ * tiles join the round's list, its converted length, frame count and end padding are the plan's.  Every append made sure
+ * the flush fits the float pool.  An allocation failure returns LAMEHIP_ERR_DEVICE with the batch as it was. */
+static int
+batch_rs_plan_finish(lamehip_batch * b)
+{
+    int const fs = fs_of(b->cfg), mfn = mfn_of(b->cfg);
+    size_t const tiles_before = b->h_tiles.size();
+    std::vector < LhRsCursor > end;
+    std::vector < int >padding;
+    try {
+        end = b->rs_cur;
+        padding.assign((size_t) b->B, 0);
+        for (int s = 0; s < b->B; s++) {
+            LhRsCursor c = b->rs_cur[(size_t) s];
+            int const nblk = lh_rs_plan_flush(b->rs, fs, mfn, &c, nullptr, 0, &padding[(size_t) s]);
+            b->rs_blk.resize((size_t) nblk);
+            (void) lh_rs_plan_flush(b->rs, fs, mfn, &end[(size_t) s], b->rs_blk.data(), nblk, &padding[(size_t) s]);
+            for (const LhRsBlock & k:b->rs_blk) {
+                size_t const at = b->h_tiles.size();
+                b->h_tiles.resize(at + (size_t) lh_rs_block_tiles(b->rs, &k, s, nullptr, 0));
+                (void) lh_rs_block_tiles(b->rs, &k, s, b->h_tiles.data() + at, (int) (b->h_tiles.size() - at));
+            }
+        }
+    }
+    catch(const std::bad_alloc &) {
+        b->h_tiles.resize(tiles_before);
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_finish: out of memory (conversion plan)");
+        return LAMEHIP_ERR_DEVICE;
+    }
+    for (int s = 0; s < b->B; s++) {
+        b->rs_cur[(size_t) s] = end[(size_t) s];
+        b->len_in[(size_t) s] = b->fed[(size_t) s] + b->staged[(size_t) s];
+        b->len[(size_t) s] = (long) end[(size_t) s].fed;
+        b->nframes[(size_t) s] = end[(size_t) s].frames;
+        b->padding[(size_t) s] = padding[(size_t) s];
+    }
+    return 0;
 }
 
 /* lame_encode_flush for every stream of an incremental batch: the frames still owed for the samples
@@ -1529,7 +1723,13 @@ lamehip_batch_finish(lamehip_batch * b)
     batch_append_time(b);
     b->ap_ms = 0;
     upto.resize((size_t) b->B);
-    for (int s = 0; s < b->B; s++) {
+    if (b->inc_rs) {
+        if ((rc = batch_rs_plan_finish(b)) != 0)
+            return rc;
+        for (int s = 0; s < b->B; s++)
+            upto[(size_t) s] = b->nframes[(size_t) s];
+    }
+    for (int s = 0; s < b->B && !b->inc_rs; s++) {
         long const len = b->fed[(size_t) s] + b->staged[(size_t) s];
         b->len[(size_t) s] = len;
         b->nframes[(size_t) s] = lh_total_frames_fs(len, fs_of(b->cfg));
@@ -1600,6 +1800,11 @@ lamehip_batch_reset(lamehip_batch * b)
         b->ap_nseg = 0;
         b->ap_max_n = 0;
         b->finished = 0;
+        /* (a batch that converts round by round: every stream's converter back in front of its first sample) */
+        for (LhRsCursor & c:b->rs_cur)
+            lh_rs_cursor_init(&c);
+        b->rs_conv.assign(b->rs_conv.size(), 0);
+        b->h_tiles.clear();
     }
     /* every gain is forgotten, and every stream with it: the next encode measures all of them again */
     b->rg_measured = 0;
@@ -2208,6 +2413,7 @@ lamehip_batch_set_device_resampling(lamehip_batch * b, int on)
     }
     if (!on || b->dev_rs) {
         b->dev_rs = on != 0 && b->dev_rs;
+        b->inc_rs = b->inc_rs && b->dev_rs;     /* (round-by-round conversion is the device converter's) */
         return 0;
     }
     /* everything new first: a failure leaves the batch as it was */
@@ -2248,6 +2454,71 @@ lamehip_batch_set_device_resampling(lamehip_batch * b, int on)
     b->tail.assign((size_t) b->B, std::vector < LhRsBlock > ());
     b->rs_dirty.assign((size_t) b->B, 0);
     b->dev_rs = 1;
+    return 0;
+}
+
+/* Incremental use of a batch that converts on the device (lamehip_batch_set_device_resampling first): the appends plan the
+ * conversion call by call, as the reference converts when lame_encode_buffer is called with the same chunks, and every round
+ * converts what was appended since the last (lh_resample_dev.hip: lh_resample_tiles_kernel).  Only before any PCM is handed
+ * over; until the first append the batch still takes whole streams (lamehip_batch_set_pcm ... lamehip_batch_encode). */
+extern "C" int
+lamehip_batch_set_incremental_resampling(lamehip_batch * b, int on)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b)
+        return -1;
+    if (!b->rate_in || !b->dev_rs) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_incremental_resampling: for a batch that converts the sample rate on the device "
+                 "(lamehip_batch_set_device_resampling first)%s", b->rate_in ? "" : ", this batch does not convert");
+        return -1;
+    }
+    if (b->pcm_given || b->encoded || b->incremental) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_incremental_resampling: only before any PCM is handed over");
+        return -1;
+    }
+    if (!on || b->inc_rs) {
+        b->inc_rs = on != 0 && b->inc_rs;
+        return 0;
+    }
+    /* everything new first: a failure leaves the batch as it was */
+    LhDevBuf < LhRsTile > tiles;
+    LhDevBuf < long long >lens;
+    std::vector < LhRsCursor > cur;
+    std::vector < long long >conv, h_lens;
+    hipError_t e = tiles.alloc(4096);
+    if (e == hipSuccess)
+        e = lens.alloc((size_t) b->B);
+    try {
+        LhRsCursor first;
+        lh_rs_cursor_init(&first);
+        cur.assign((size_t) b->B, first);
+        conv.assign((size_t) b->B, 0);
+        h_lens.assign((size_t) b->B, 0);
+    }
+    catch(const std::bad_alloc &) {
+        e = hipErrorOutOfMemory;
+    }
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        return set_err("lamehip_batch_set_incremental_resampling: allocation", e);
+    }
+    b->d_tiles = std::move(tiles);
+    b->d_rs_lens = std::move(lens);
+    b->rs_cur = std::move(cur);
+    b->rs_conv = std::move(conv);
+    b->h_rs_lens = std::move(h_lens);
+    b->h_tiles.clear();
+    b->inc_capf = b->capf;
+    {
+        /* LAMEHIP_INC_RS_ROOM=n, looked at here: the appends count the float pool as n converted samples per stream, no more
+         * than it has (test aid: the pool's own margin, 4 * 1152 + 64, holds the flush of every stream that fits the input
+         * capacity, so the appends' second refusal needs a smaller figure to be met) */
+        const char *e = getenv("LAMEHIP_INC_RS_ROOM");
+        long const room = e ? strtol(e, nullptr, 10) : 0;
+        if (room > 0 && room < b->capf)
+            b->inc_capf = room;
+    }
+    b->inc_rs = 1;
     return 0;
 }
 
@@ -2327,7 +2598,7 @@ lamehip_batch_get_converted(lamehip_batch * b, int s, float *l, float *r, long c
         return -1;
     }
     /* (an incremental typed batch: the float planes up to what has reached the pool) */
-    long const n = b->incremental ? b->fed[(size_t) s] : b->len[(size_t) s];
+    long const n = !b->incremental ? b->len[(size_t) s] : b->inc_rs ? (long) b->rs_conv[(size_t) s] : b->fed[(size_t) s];
     if (n > cap)
         return -1;
     HIPCHK(hipStreamSynchronize(b->stream));

@@ -200,6 +200,19 @@ int     lh_rs_plan_tail(const LhResampler * r, const LhRsTrunk * t, long n, LhRs
 /* trunk prefix and tail of one stream in one list (at most `cap' written); *ntrunk = length of the prefix */
 int     lh_rs_plan(const LhResampler * r, int fs, int mfn, long n, LhRsBlock * out, int cap, int *ntrunk, long *conv_len,
                    int *frames, int *padding);
+/* The plan of a stream fed call by call (an incremental batch), from a cursor of its own: lh_rs_cursor_init is the
+ * converter before its first sample (what the trunk's after[0] holds).
+ * lh_rs_plan_call: one lame_encode_buffer call of m input samples at the cursor -- blocks of want = fs and len = what is
+ * left of the call until the call is used up --; the cursor advances past the call.
+ * lh_rs_plan_flush: the flush from the cursor -- the frames still owed, fed with bunches of zeros --; *padding is the
+ * end padding, the cursor ends at the stream's converted length and frame count.
+ * Both return the number of blocks and write only the first `cap' (blk == NULL: none). */
+void    lh_rs_cursor_init(LhRsCursor * c);
+int     lh_rs_plan_call(const LhResampler * r, int fs, int mfn, LhRsCursor * c, int m, LhRsBlock * blk, int cap);
+int     lh_rs_plan_flush(const LhResampler * r, int fs, int mfn, LhRsCursor * c, LhRsBlock * blk, int cap, int *padding);
+/* the tiles of one block, in output order: each as many outputs as touch at most LH_RS_SPAN_MAX input positions, measured
+ * with lh_rs_locate; none for a block that makes nothing.  Returns their number, only the first `cap' are written */
+int     lh_rs_block_tiles(const LhResampler * r, const LhRsBlock * b, int stream, LhRsTile * tiles, int cap);
 /* one block of a plan evaluated on the host, sample by sample as the device kernel does it: writes
  * out_l / out_r [out_at, out_at + made) */
 void    lh_rs_eval_block(const LhResampler * r, const LhRsBlock * b, int channels, float pcm_scale, float pcm_mix,

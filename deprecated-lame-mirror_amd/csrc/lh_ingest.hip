@@ -138,7 +138,9 @@ lh_deinterleave_kernel(const T * src_l, const T * src_r, T * dst_l, T * dst_r, l
  * A table of segments (LhApSeg, lh_pcm_in.h), each a chunk of one stream in the batch's element type -- in the staging
  * arena or in the caller's own device buffers, planar or interleaved -- goes to its place in the pool the kernels read:
  * an int32 / float chunk through lh_rs_mix into the float pool, what lh_ingest_kernel would have written at the same
- * positions; an s16 chunk as it is into the s16 pool (the front kernels apply the matrix, as for lamehip_batch_append).
+ * positions; an s16 chunk as it is into the s16 pool (the front kernels apply the matrix, as for lamehip_batch_append);
+ * and a chunk of a batch that converts the rate round by round as it is into the INPUT pool, whatever its type (4-byte
+ * elements as uint32_t: the converter applies matrix and norm, lh_resample_dev.hip).
  *
  * The same stream as the ingest, in UNITS of 16 destination bytes (four floats, eight shorts).  A segment's `at' moves
  * the destination's alignment independently of the row's, so p0 -- the first position at which the left destination
@@ -205,9 +207,22 @@ template < typename T > struct LhApDst {
 template <> struct LhApDst <int16_t > {
     typedef int16_t type;
 };
+/* (uint32_t: a 4-byte element as it is -- the int32 / float input pool of a batch that converts the rate round by round,
+ * whose converter applies the matrix and the type's norm; bits are moved, nothing is computed) */
+template <> struct LhApDst <uint32_t > {
+    typedef uint32_t type;
+};
 
 LH_RS_FN void
 ap_put(int16_t xl, int16_t xr, const LhInParams & p, int16_t * u, int16_t * v)
+{
+    (void) p;
+    *u = xl;
+    *v = xr;
+}
+
+LH_RS_FN void
+ap_put(uint32_t xl, uint32_t xr, const LhInParams & p, uint32_t * u, uint32_t * v)
 {
     (void) p;
     *u = xl;
@@ -367,6 +382,29 @@ lh_launch_append(int type, const LhInParams * p, const LhApSeg * segs, int nsegs
     return 0;
 }
 
+/* the same into an INPUT pool of elements of esz bytes (2 or 4), every sample as it is: p->m and p->channels are not used,
+ * p->cap is the input pool's row length.  Returns a hipError_t. */
+extern "C" int
+lh_launch_append_raw(int esz, const LhInParams * p, const LhApSeg * segs, int nsegs, long long max_n, void *pool, void *stream)
+{
+    if (nsegs <= 0 || max_n <= 0)
+        return 0;
+    if ((esz != 2 && esz != 4) || max_n > p->cap)
+        return (int) hipErrorInvalidValue;
+    for (int at = 0; at < nsegs; at += 65535) {
+        int const ns = nsegs - at < 65535 ? nsegs - at : 65535;
+        dim3 const grid(append_blocks(max_n, 16 / esz), (unsigned) ns), block(LH_IN_NT);
+        if (esz == 2)
+            hipLaunchKernelGGL((lh_append_kernel < int16_t >), grid, block, 0, (hipStream_t) stream, *p, segs + at, pool);
+        else
+            hipLaunchKernelGGL((lh_append_kernel < uint32_t >), grid, block, 0, (hipStream_t) stream, *p, segs + at, pool);
+        hipError_t const e = hipGetLastError();
+        if (e != hipSuccess)
+            return (int) e;
+    }
+    return 0;
+}
+
 /* elements of esz bytes (2 or 4).  Returns a hipError_t. */
 extern "C" int
 lh_launch_deinterleave(int esz, const void *src_l, const void *src_r, void *dst_l, void *dst_r, long long n, void *stream)
@@ -421,6 +459,25 @@ lh_emu_append(int type, const LhInParams * params, const LhApSeg * segs, int nse
                    lh_append_kernel < int32_t > (p, segs, pool);
                else
                    lh_append_kernel < float >(p, segs, pool);
+               }
+    );
+    return 0;
+}
+
+extern "C" int
+lh_emu_append_raw(int esz, const LhInParams * params, const LhApSeg * segs, int nsegs, long long max_n, void *pool)
+{
+    LhInParams const p = *params;
+    hipemu_dim3 grid = { append_blocks(max_n, esz == 2 ? 8 : 4), (unsigned) nsegs, 1 }, block = { LH_IN_NT, 1, 1 };
+    if (nsegs <= 0 || max_n <= 0)
+        return 0;
+    if ((esz != 2 && esz != 4) || max_n > p.cap)
+        return -1;
+    hipemu_run(grid, block,[=] () {
+               if (esz == 2)
+                   lh_append_kernel < int16_t > (p, segs, pool);
+               else
+                   lh_append_kernel < uint32_t > (p, segs, pool);
                }
     );
     return 0;

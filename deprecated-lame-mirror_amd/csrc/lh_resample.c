@@ -478,6 +478,82 @@ lh_rs_plan(const LhResampler * r, int fs, int mfn, long n, LhRsBlock * out, int 
     return ntail < 0 ? -1 : k + ntail;
 }
 
+/* ---- the plan of a stream that is fed call by call (an incremental batch) -------------------------
+ * Where the reference cuts its blocks depends on how lame_encode_buffer was called, so this plan follows the calls:
+ * a cursor per stream, advanced by every call and at last by the flush.  The arithmetic is rs_plan_feed's, the same the
+ * whole-stream plan above is made of. */
+
+void
+lh_rs_cursor_init(LhRsCursor * c)
+{
+    memset(c, 0, sizeof(*c));
+    c->mf_size = LH_MF_START;
+}
+
+int
+lh_rs_plan_call(const LhResampler * r, int fs, int mfn, LhRsCursor * c, int m, LhRsBlock * blk, int cap)
+{
+    RsList  list;
+    list.blk = blk;
+    list.cap = blk ? cap : 0;
+    list.n = 0;
+    rs_plan_feed(r, fs, mfn, c, m, &list);
+    return (int) list.n;
+}
+
+int
+lh_rs_plan_flush(const LhResampler * r, int fs, int mfn, LhRsCursor * c, LhRsBlock * blk, int cap, int *padding)
+{
+    RsList  list;
+    int     frames_left = rs_frames_left(r->ratio, fs, c->fed, c->frames, padding);
+    list.blk = blk;
+    list.cap = blk ? cap : 0;
+    list.n = 0;
+    while (frames_left > 0) {
+        int const before = c->frames;
+        rs_plan_feed(r, fs, mfn, c, rs_flush_bunch(r->ratio, mfn, c->mf_size), &list);
+        frames_left -= (c->frames != before) ? 1 : 0;
+    }
+    return (int) list.n;
+}
+
+/* input positions outputs [k0, k0 + count) of a block touch, first tap of the first to last tap of the last */
+static int
+rs_tile_span(const LhResampler * r, double start, int k0, int count)
+{
+    return rs_reach(r, start, k0 + count - 1) + 1 - rs_locate(r, start, k0).first;
+}
+
+int
+lh_rs_block_tiles(const LhResampler * r, const LhRsBlock * b, int stream, LhRsTile * tiles, int cap)
+{
+    /* (floor(k ratio - start) is monotone in k, so a tile's span is in its count: an estimate from the ratio, corrected
+     * with the exact expression) */
+    double const guess = (LH_RS_SPAN_MAX - r->taps - 1) / r->ratio;
+    int     k0 = 0, n = 0;
+    while (k0 < b->made) {
+        int const left = b->made - k0;
+        int     count = guess < 1 ? 1 : guess > left ? left : (int) guess;
+        while (count > 1 && rs_tile_span(r, b->start, k0, count) > LH_RS_SPAN_MAX)
+            count--;
+        while (count < left && rs_tile_span(r, b->start, k0, count + 1) <= LH_RS_SPAN_MAX)
+            count++;
+        if (tiles && n < cap) {
+            LhRsTile *t = &tiles[n];
+            t->in_at = b->in_at;
+            t->out_at = b->out_at + k0;
+            t->start = b->start;
+            t->k0 = k0;
+            t->count = count;
+            t->stream = stream;
+            t->pad_ = 0;
+        }
+        n++;
+        k0 += count;
+    }
+    return n;
+}
+
 /* input sample `at' (absolute) of the stream behind the PCM matrix: zero outside [0, n) */
 static void
 rs_input(const LhRsMatrix * mx, const short *l, const short *rr, long n, long long at, float *xl_out, float *xr_out)

@@ -13,6 +13,8 @@
  *
  * The bank of kernels is read through the vector cache, rows of LH_RS_ROW floats fetched 16 bytes at a time (a
  * copy of the bank in LDS, loaded once per workgroup for a run of blocks, measured 2.5 times slower: DESIGN.md).
+ *
+ * An incremental batch converts round by round with lh_resample_tiles_kernel (further down, with its own notes).
  * Built with -ffp-contract=off like every object of the library.
  */
 #include <stdint.h>
@@ -103,7 +105,107 @@ lh_resample_kernel(LhRsParams p, const float *bank, const LhRsBlock * trunk, con
     rs_convert_block < TAPS, T > (p, bank, blk, sd.n, in_l, in_r, out_l, out_r, xs);
 }
 
+/* ---- lh_resample_tiles_kernel: the converter of an incremental batch (lamehip_batch_set_incremental_resampling) ----
+ * A stream fed call by call is cut into blocks where the calls fall (lh_rs_plan_call), and a block of such a stream may
+ * touch more input than LDS holds for one: the work is a TILE (LhRsTile), a run of a block's outputs whose input span the
+ * host has measured to fit.  One workgroup per tile of a flat table for the whole round -- a round is ragged, most streams
+ * bring a few tiles and some none --, the stream's input length from a table indexed by the tile's stream.  Staging and the
+ * sums are those of rs_convert_block; the outputs are located from the BLOCK's start (k0 + k), which is what makes the
+ * tiles of a block give the block's floats. */
+template < int TAPS, typename T >
 #ifndef LH_EMU
+__global__ void __launch_bounds__(LH_RS_NT)
+#else
+void
+#endif
+lh_resample_tiles_kernel(LhRsParams p, const float *bank, const LhRsTile * tiles, const long long *lens, const T * pcm, float *pcmf)
+{
+    __shared__ float xs[2][LH_RS_SPAN_MAX];
+    LhRsTile const tl = tiles[blockIdx.x];
+    int const tid = (int) threadIdx.x;
+    if (tl.count <= 0)
+        return;
+    /* nothing at or beyond the stream's length is read, nor beyond its row whatever the table says */
+    long long const n = lens[tl.stream] < p.cap_in ? lens[tl.stream] : p.cap_in;
+    const T *in_l = pcm + (size_t) tl.stream * 2 * (size_t) p.cap_in, *in_r = in_l + p.cap_in;
+    float  *out_l = pcmf + (size_t) tl.stream * 2 * (size_t) p.cap_out, *out_r = out_l + p.cap_out;
+    /* the span of input the tile touches, from the first tap of its first output to the last of its last */
+    int const lo = lh_rs_locate(p.ratio, TAPS, p.phases, tl.start, tl.k0).first;
+    int const span = lh_rs_locate(p.ratio, TAPS, p.phases, tl.start, tl.k0 + tl.count - 1).first + TAPS + 1 - lo;
+    if (span > LH_RS_SPAN_MAX || tl.out_at < 0 || tl.out_at + tl.count > p.cap_out)
+        return;                 /* (no tile of the host's is such: lh_rs_block_tiles, and the appends' capacity check) */
+    for (int t = tid; t < span; t += LH_RS_NT) {
+        long long const at = tl.in_at + lo + t;
+        float   xl = 0.0f, xr = 0.0f;
+        if (at >= 0 && at < n) {
+            float const sl = (float) in_l[at], sr = p.one_plane ? sl : (float) in_r[at];
+            xl = lh_rs_mix(sl, sr, p.m.m00, p.m.m01);
+            xr = lh_rs_mix(sl, sr, p.m.m10, p.m.m11);
+        }
+        xs[0][t] = xl;
+        xs[1][t] = xr;
+    }
+    __syncthreads();
+    for (int k = tid; k < tl.count; k += LH_RS_NT) {
+        LhRsSpot const s = lh_rs_locate(p.ratio, TAPS, p.phases, tl.start, tl.k0 + k);
+        const float *x0 = xs[0] + (s.first - lo), *x1 = xs[1] + (s.first - lo);
+        float   a0 = 0.f, a1 = 0.f;
+        const LhRsF4 *row = (const LhRsF4 *) (bank + (size_t) s.kernel * LH_RS_ROW);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            LhRsF4 const w = row[q];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                a0 = LH_RS_FADD(a0, LH_RS_FMUL(x0[4 * q + j], w.v[j]));
+                a1 = LH_RS_FADD(a1, LH_RS_FMUL(x1[4 * q + j], w.v[j]));
+            }
+        }
+        if (TAPS == 32) {
+            float const w = bank[(size_t) s.kernel * LH_RS_ROW + 32];
+            a0 = LH_RS_FADD(a0, LH_RS_FMUL(x0[32], w));
+            a1 = LH_RS_FADD(a1, LH_RS_FMUL(x1[32], w));
+        }
+        out_l[tl.out_at + k] = a0;
+        out_r[tl.out_at + k] = p.channels == 1 ? 0.0f : a1;
+    }
+}
+
+#ifndef LH_EMU
+template < typename T > static int
+rs_launch_tiles(const LhRsParams * p, const float *bank, const LhRsTile * tiles, long long ntiles, const long long *lens, const T * pcm,
+                float *pcmf, void *stream)
+{
+    if (ntiles <= 0)
+        return 0;
+    if ((p->taps != 31 && p->taps != 32) || p->phases < 1 || p->phases > 320 || ntiles > 0x7fffffffLL)
+        return (int) hipErrorInvalidValue;
+    dim3 const grid((unsigned) ntiles), block(LH_RS_NT);
+    if (p->taps == 31)
+        hipLaunchKernelGGL((lh_resample_tiles_kernel < 31, T >), grid, block, 0, (hipStream_t) stream, *p, bank, tiles, lens, pcm, pcmf);
+    else
+        hipLaunchKernelGGL((lh_resample_tiles_kernel < 32, T >), grid, block, 0, (hipStream_t) stream, *p, bank, tiles, lens, pcm, pcmf);
+    return (int) hipGetLastError();
+}
+
+/* ntiles entries of `tiles' (device), every tile's stream an index into `lens' (device: input samples per stream); `pcm' is
+ * a pool of `type' (LH_PCM_*), whose norm the caller has put into p->m (lh_pcm_matrix; lh_rs_matrix for s16).  The caller
+ * has checked every tile against the float pool's rows.  Returns a hipError_t. */
+extern "C" int
+lh_launch_resample_tiles(int type, const LhRsParams * p, const float *bank, const LhRsTile * tiles, long long ntiles,
+                         const long long *lens, const void *pcm, float *pcmf, void *stream)
+{
+    switch (type) {
+    case LH_PCM_S16:
+        return rs_launch_tiles(p, bank, tiles, ntiles, lens, (const int16_t *) pcm, pcmf, stream);
+    case LH_PCM_S32:
+        return rs_launch_tiles(p, bank, tiles, ntiles, lens, (const int32_t *) pcm, pcmf, stream);
+    case LH_PCM_F32:
+    case LH_PCM_F32_UNIT:
+        return rs_launch_tiles(p, bank, tiles, ntiles, lens, (const float *) pcm, pcmf, stream);
+    }
+    return (int) hipErrorInvalidValue;
+}
+
 template < typename T > static int
 rs_launch(const LhRsParams * p, const float *bank, const LhRsBlock * trunk, const LhRsBlock * tails, const LhRsStream * streams,
           int nstreams, int max_blocks, const T * pcm, float *pcmf, void *stream)
@@ -185,6 +287,40 @@ lh_emu_resample_typed(int type, const LhRsParams * params, const float *bank, co
     case LH_PCM_F32:
     case LH_PCM_F32_UNIT:
         return rs_emu(params, bank, trunk, tails, streams, nstreams, max_blocks, (const float *) pcm, pcmf);
+    }
+    return -1;
+}
+
+template < typename T > static int
+rs_emu_tiles(const LhRsParams * params, const float *bank, const LhRsTile * tiles, long long ntiles, const long long *lens, const T * pcm,
+             float *pcmf)
+{
+    LhRsParams const p = *params;
+    hipemu_dim3 grid = { (unsigned) ntiles, 1, 1 }, block = { LH_RS_NT, 1, 1 };
+    if (ntiles <= 0)
+        return 0;
+    hipemu_run(grid, block,[=] () {
+               if (p.taps == 31)
+                   lh_resample_tiles_kernel < 31, T > (p, bank, tiles, lens, pcm, pcmf);
+               else
+                   lh_resample_tiles_kernel < 32, T > (p, bank, tiles, lens, pcm, pcmf);
+               }
+    );
+    return 0;
+}
+
+extern "C" int
+lh_emu_resample_tiles(int type, const LhRsParams * params, const float *bank, const LhRsTile * tiles, long long ntiles,
+                      const long long *lens, const void *pcm, float *pcmf)
+{
+    switch (type) {
+    case LH_PCM_S16:
+        return rs_emu_tiles(params, bank, tiles, ntiles, lens, (const int16_t *) pcm, pcmf);
+    case LH_PCM_S32:
+        return rs_emu_tiles(params, bank, tiles, ntiles, lens, (const int32_t *) pcm, pcmf);
+    case LH_PCM_F32:
+    case LH_PCM_F32_UNIT:
+        return rs_emu_tiles(params, bank, tiles, ntiles, lens, (const float *) pcm, pcmf);
     }
     return -1;
 }

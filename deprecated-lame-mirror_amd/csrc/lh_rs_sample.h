@@ -48,7 +48,21 @@ typedef struct LhRsStream {
     int     ntail;
 } LhRsStream;
 
-#define LH_RS_ROW 36            /* floats per kernel of the device's bank in HBM: rows start on 16-byte boundaries */
+/* A tile of an incremental conversion (lh_rs_block_tiles; lh_resample_dev.hip: lh_resample_tiles_kernel): outputs
+ * [k0, k0 + count) of the block that starts at clock `start' with its position 0 at in_at go to out_at on (the block's
+ * out_at + k0).  A tile is cut so that the input its outputs touch fits LH_RS_SPAN_MAX; lh_rs_locate counts from the
+ * block's start, so a block cut into tiles gives the floats of the block done whole. */
+typedef struct LhRsTile {
+    long long in_at;
+    long long out_at;
+    double  start;
+    int     k0;
+    int     count;
+    int     stream;             /* row pair of the pools, and the entry of the launch's table of input lengths */
+    int     pad_;
+} LhRsTile;
+
+#define LH_RS_ROW 36           /* floats per kernel of the device's bank in HBM: rows start on 16-byte boundaries */
 /* input positions a block's outputs can touch: its len <= 1152 samples and the taps + 1 <= 33 before them */
 #define LH_RS_SPAN_MAX 1216
 

@@ -426,11 +426,25 @@ class Batch:
         if rc:
             raise RuntimeError("lamehip_batch_set_device_resampling failed (%d): %s" % (rc, last_error()))
 
+    def set_incremental_resampling(self, on=True):
+        """Incremental use of a batch that converts on the device (set_device_resampling() first): append() /
+        append_input() / append_device() then take chunks at the input rate, each one call of the reference entry point,
+        converter included, and encode_available() / finish() convert what came since the last round with one launch
+        (resample_ms()).  Before any PCM is handed over."""
+        self.lib.lamehip_batch_set_incremental_resampling.argtypes = [C.c_void_p, C.c_int]
+        rc = self.lib.lamehip_batch_set_incremental_resampling(self.b, 1 if on else 0)
+        if rc:
+            raise RuntimeError("lamehip_batch_set_incremental_resampling failed (%d): %s" % (rc, last_error()))
+
     def converted(self, s):
         """The converted signal of stream s as the encoder reads it: float32 [2, converted length] (test accessor)."""
         self.lib.lamehip_batch_get_converted.restype = C.c_long
         self.lib.lamehip_batch_get_converted.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
         cap = max((self.frames(s) + 4) * 1152, self.capacity)    # (an incremental batch knows its frames at finish())
+        h = getattr(self.enc, "h", None)
+        rate_in, rate_out = (self.lib.lame_get_in_samplerate(h), self.lib.lame_get_out_samplerate(h)) if h else (0, 0)
+        if 0 < rate_in < rate_out:     # (one that converts upwards holds more than its capacity of input samples)
+            cap = max(cap, self.capacity * rate_out // rate_in + 4 * 1152 + 64)
         out = np.zeros((2, cap), dtype=np.float32)
         n = self.lib.lamehip_batch_get_converted(self.b, s, out[0].ctypes.data, out[1].ctypes.data, cap)
         if n < 0:

@@ -248,17 +248,34 @@ int     lamehip_batch_set_length(lamehip_batch *, int stream, long nsamples);
  * lamehip_batch_encode converts the streams declared (lamehip_batch_set_pcm* / _set_length / _mark_pcm) since their
  * last conversion with a kernel on the batch's stream, in front of the analysis kernels.  Samples at or beyond a
  * stream's length are never read.  Same floats, hence same bytes, as the host conversion.  An allocation failure
- * returns LAMEHIP_ERR_DEVICE and leaves the batch as it was.  lamehip_batch_append stays refused on a converting
- * batch either way. */
+ * returns LAMEHIP_ERR_DEVICE and leaves the batch as it was.  lamehip_batch_append and the other incremental calls
+ * stay refused on a converting batch unless lamehip_batch_set_incremental_resampling (below) opens them. */
 int     lamehip_batch_set_device_resampling(lamehip_batch *, int on);
+/* Incremental use of a batch that converts the rate on the device: a live producer at one rate, the encoder at another.
+ * Accepted only with lamehip_batch_set_device_resampling on (-1 otherwise, lamehip_last_error() names that call) and only
+ * before any PCM, length or mirror has been handed over; before or after lamehip_batch_set_sample_type.  With it on,
+ * lamehip_batch_append (an s16 batch), lamehip_batch_append_input, _append_input_device and _append_device take chunks
+ * at the INPUT rate in the batch's element type: every call is one call of the reference entry point the type is named
+ * after, converter included -- the reference cuts a call into blocks of at most one frame of output and carries its
+ * clock and filter tail from call to call, so the bytes depend on how the stream is cut into calls, and
+ * lamehip_batch_drain hands over the bytes that call would have returned.  The chunks land in the input pool as they
+ * are; lamehip_batch_encode_available and lamehip_batch_finish convert what was appended since the last round with ONE
+ * kernel launch (lamehip_batch_last_resample_ms: that launch) in front of the encode launch, lamehip_batch_finish also
+ * the flush.  Capacity counts input samples; an append is also refused (-1, nothing counted) when its stream, flushed
+ * right after the call, would exceed the float pool -- lamehip_batch_finish therefore never lacks room.  Device packing
+ * and ReplayGain stay refused on an incremental batch.  Until the first append the batch takes whole streams as before.
+ * An allocation failure returns LAMEHIP_ERR_DEVICE and leaves the batch as it was. */
+int     lamehip_batch_set_incremental_resampling(lamehip_batch *, int on);
 /* test accessor: the converted signal of a stream (float planes as the encoder reads them), valid after
  * lamehip_batch_set_pcm when the host converts and after lamehip_batch_encode when the device does -- also the float
  * planes of a batch of another sample type that does not convert, after lamehip_batch_encode, or, on an incremental
  * batch of such a type, up to what has reached the pool (device-resident appends at once, staged ones with the next
- * lamehip_batch_encode_available / _finish) --; waits for the batch's stream.  Returns the converted length, or a negative code (-1 also when it exceeds cap). */
+ * lamehip_batch_encode_available / _finish), and on an incremental batch that converts, what the rounds so far have
+ * converted --; waits for the batch's stream.  Returns the converted length, or a negative code (-1 also when it exceeds cap). */
 long    lamehip_batch_get_converted(lamehip_batch *, int stream, float *l, float *r, long cap);
-/* HIP-event time in ms of the device conversion of the last lamehip_batch_encode (after lamehip_batch_sync); 0 when
- * none ran.  It is not part of lamehip_batch_last_kernel_ms / _parts_ms. */
+/* HIP-event time in ms of the device conversion of the last lamehip_batch_encode (after lamehip_batch_sync), or of the
+ * last lamehip_batch_encode_available / _finish of an incremental batch that converts; 0 when none ran.  It is not part
+ * of lamehip_batch_last_kernel_ms / _parts_ms. */
 float   lamehip_batch_last_resample_ms(lamehip_batch *);
 
 /* Sample types of a batch's input, each named after the reference entry point whose bytes it reproduces (lame.c:1786-1972:
@@ -342,8 +359,10 @@ int     lamehip_batch_finish(lamehip_batch *);
  * The first call switches the batch to incremental use whatever its sample type; capacity, lamehip_batch_finish /
  * lamehip_batch_reset and lamehip_batch_drain are as above.  lamehip_batch_append (shorts) stays refused on a batch of
  * another type.  -1, with a lamehip_last_error() that names the call: a stream that would exceed the capacity, a stride
- * other than 1 or 2, a finished batch, a batch that converts the sample rate, packs on the device or measures ReplayGain
- * (the conversion plan and the gain plan depend on how the reference is called chunk by chunk: not built yet).
+ * other than 1 or 2, a finished batch, a batch that converts the sample rate without
+ * lamehip_batch_set_incremental_resampling (with it the chunks are at the input rate and go to the input pool as they
+ * are, see there), a batch that packs on the device or measures ReplayGain (the gain plan depends on how the reference is
+ * called chunk by chunk: not built yet).
  * LAMEHIP_ERR_DEVICE when an allocation fails, the batch is then as it was.
  *   lamehip_batch_append_input         host buffers, l and r `stride' elements from sample to sample as for
  *                                      lamehip_batch_set_input; staged in the pinned arena like the shorts of
