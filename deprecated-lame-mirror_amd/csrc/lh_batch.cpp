@@ -25,6 +25,8 @@ extern "C" int lh_launch_resample_tiles(int type, const LhRsParams * p, const fl
 extern "C" int lh_launch_deinterleave(int esz, const void *src_l, const void *src_r, void *dst_l, void *dst_r, long long n, void *stream);
 extern "C" int lh_launch_gain(int floats, const LhGainParams * p, const LhGainStream * streams, int nstreams, const int *trunk, const int *tails,
                               const void *pool, double *pairs, void *stream);
+extern "C" int lh_launch_gain_resume(int floats, const LhGainParams * p, const LhGainStream * streams, int nstreams, const int *tails,
+                                     const void *pool, double *pairs, LhGainCarry * carry, void *stream);
 extern "C" void lh_pcm_copy_plane(void *dst, const void *src, int esz, int stride, long n);
 
 /* per device: the end of the last launch that filled it (lamehip_batch_encode) */
@@ -154,6 +156,20 @@ struct lamehip_batch {
     LhEvent ev_rg[2];
     int     rg_ran = 0;         /* the last lamehip_batch_encode analysed something (between ev_rg[0] and ev_rg[1]) */
     float   rg_ms = 0;
+    /* ... or, after lamehip_batch_set_incremental_replaygain, round by round once the batch is fed with appends: every append
+     * is planned at once as the call to the analysis it is (lh_gain_plan_call from the stream's cursor; a batch that converts:
+     * the made counts of the conversion's call plan), lamehip_batch_encode_available / _finish run ONE launch of
+     * lh_gain_resume_kernel over the blocks planned since the last round, behind the append and conversion launches, and the
+     * round's window sums come home with the round's wait.  What a stream carries between rounds stays in HBM (LhGainCarry). */
+    int     inc_rg = 0;
+    int     rg_was_on = 0;      /* rg_on as it was before the switch (which sets it: until the first append whole streams are measured) */
+    int     rg_closed = 0;      /* lamehip_batch_finish has analysed the flush: the gains are final */
+    long long inc_rg_max = 0;   /* samples of a stream the analysis takes: LH_GN_MAX_TOTAL (less under LAMEHIP_INC_RG_MAX) */
+    std::vector < LhGainCursor > rg_cur;        /* per stream: the analysis behind the calls so far (a batch that converts: rs_cur) */
+    std::vector < std::vector < int > >rg_blk;  /* per stream: the blocks planned since the last round */
+    std::vector < long long >rg_heard;  /* per stream: samples the rounds so far have analysed (the carry's `heard') */
+    std::vector < double >h_rg_round;   /* the round's window sums, on their way home */
+    LhDevBuf < LhGainCarry > d_rg_carry;
     /* incremental use (lamehip_batch_append ...): samples in the pool / frames encoded per stream, a
      * packer and the bytes not yet drained per stream, and the pinned staging area of the next
      * lamehip_batch_encode_available (see h_stage below) */
@@ -991,6 +1007,31 @@ batch_incremental_check(const lamehip_batch * b, const char *who, int typed_ok)
     return 0;
 }
 
+/* A batch that measures ReplayGain round by round starts (over): every stream's analysis in front of its first sample --
+ * cursors, the blocks planned, the carry in HBM (on the batch's stream, in front of the first round's launch) --, no window,
+ * no gain; whatever lamehip_batch_encode measured of whole streams before the first append is forgotten. */
+static int
+batch_gain_restart(lamehip_batch * b)
+{
+    if (!b->inc_rg)
+        return 0;
+    HIPCHK(hipMemsetAsync(b->d_rg_carry.get(), 0, (size_t) b->B * sizeof(LhGainCarry), b->stream));
+    for (LhGainCursor & c:b->rg_cur)
+        lh_gain_cursor_init(&c);
+    for (std::vector < int >&g:b->rg_blk)
+        g.clear();
+    b->rg_heard.assign((size_t) b->B, 0);
+    for (std::vector < double >&w:b->rg_win)
+        w.clear();
+    b->rg_tenths.assign((size_t) b->B, 0);
+    b->rg_closed = 0;
+    b->rg_measured = 0;
+    b->rg_pending = 0;
+    b->rg_ran = 0;
+    b->rg_ms = 0;
+    return 0;
+}
+
 static int
 batch_incremental_begin(lamehip_batch * b, const char *who, int typed_ok)
 {
@@ -998,7 +1039,7 @@ batch_incremental_begin(lamehip_batch * b, const char *who, int typed_ok)
         return 0;
     if (batch_incremental_check(b, who, typed_ok) != 0)
         return -1;
-    if (batch_reset_states(b) != 0)
+    if (batch_reset_states(b) != 0 || batch_gain_restart(b) != 0)
         return LAMEHIP_ERR_DEVICE;
     b->fed.assign((size_t) b->B, 0);
     b->done.assign((size_t) b->B, 0);
@@ -1014,11 +1055,12 @@ batch_incremental_begin(lamehip_batch * b, const char *who, int typed_ok)
     return 0;
 }
 
-/* a batch that measures ReplayGain is encoded whole (lamehip_batch_encode): the analysis runs once per stream */
+/* a batch that measures ReplayGain is encoded whole (lamehip_batch_encode): the analysis runs once per stream -- refused
+ * unless lamehip_batch_set_incremental_replaygain has the analysis follow the calls */
 static int
 batch_refuse_gain(const lamehip_batch * b, const char *who)
 {
-    if (!b->rg_on)
+    if (!b->rg_on || b->inc_rg) /* (lamehip_batch_set_incremental_replaygain: measured round by round) */
         return 0;
     snprintf(g_err, sizeof(g_err), "%s: this batch measures ReplayGain (lamehip_batch_set_replaygain), which incremental use does not", who);
     return 1;
@@ -1183,6 +1225,21 @@ batch_rs_plan_append(lamehip_batch * b, const char *who, int s, int n, bool comm
                  "%ld per stream", who, s, end.fed, b->inc_capf);
         return -1;
     }
+    /* (ReplayGain round by round: the analysis hears the converted samples, in the blocks they are made in) */
+    if (b->inc_rg) {
+        if (end.fed > b->inc_rg_max) {
+            snprintf(g_err, sizeof(g_err), "%s: stream %d, flushed behind this call, would be %lld samples: more than the ReplayGain analysis "
+                     "takes (%lld)", who, s, end.fed, b->inc_rg_max);
+            return -1;
+        }
+        try {
+            b->rg_blk[(size_t) s].reserve(b->rg_blk[(size_t) s].size() + b->rs_blk.size());
+        }
+        catch(const std::bad_alloc &) {
+            snprintf(g_err, sizeof(g_err), "%s: out of memory (gain plan)", who);
+            return LAMEHIP_ERR_DEVICE;
+        }
+    }
     for (const LhRsBlock & k:b->rs_blk)
         nt += (size_t) lh_rs_block_tiles(b->rs, &k, s, nullptr, 0);
     if (ntiles)
@@ -1200,7 +1257,47 @@ batch_rs_plan_append(lamehip_batch * b, const char *who, int s, int n, bool comm
     nt = at;
     for (const LhRsBlock & k:b->rs_blk)
         nt += (size_t) lh_rs_block_tiles(b->rs, &k, s, b->h_tiles.data() + nt, (int) (b->h_tiles.size() - nt));
+    if (b->inc_rg)
+        for (const LhRsBlock & k:b->rs_blk)
+            if (k.made > 0)
+                b->rg_blk[(size_t) s].push_back(k.made);        /* (room was made above) */
     b->rs_cur[(size_t) s] = c;
+    return 0;
+}
+
+/* A batch that measures ReplayGain round by round and does not convert: the append of n samples to stream s is one
+ * lame_encode_buffer call to the analysis, planned here from the stream's cursor (lh_gain_plan_call; a batch that converts has
+ * it from batch_rs_plan_append).  Refused (-1, `who' in the message) when the stream, flushed right after this call, would be
+ * longer than the analysis takes.  commit: the cursor advances and the call's blocks join the round's; else the call is only
+ * checked and room made for its blocks.  An allocation failure returns LAMEHIP_ERR_DEVICE; a call that does not return 0
+ * leaves the batch as it was. */
+static int
+batch_rg_plan_append(lamehip_batch * b, const char *who, int s, int n, bool commit)
+{
+    if (!b->inc_rg || b->inc_rs)
+        return 0;
+    int const fs = fs_of(b->cfg), mfn = mfn_of(b->cfg);
+    LhGainCursor c = b->rg_cur[(size_t) s], end;
+    int const nblk = lh_gain_plan_call(&c, fs, mfn, n, nullptr, 0);
+    end = c;
+    if (nblk < 0 || lh_gain_plan_flush(&end, fs, mfn, nullptr, 0) < 0 || end.heard > b->inc_rg_max) {
+        snprintf(g_err, sizeof(g_err), "%s: stream %d, flushed behind this call, would be %lld samples: more than the ReplayGain analysis "
+                 "takes (%lld)", who, s, nblk < 0 ? -1LL : end.heard, b->inc_rg_max);
+        return -1;
+    }
+    std::vector < int >&g = b->rg_blk[(size_t) s];
+    size_t const at = g.size();
+    try {
+        g.reserve(at + (size_t) nblk);
+    }
+    catch(const std::bad_alloc &) {
+        snprintf(g_err, sizeof(g_err), "%s: out of memory (gain plan)", who);
+        return LAMEHIP_ERR_DEVICE;
+    }
+    if (!commit)
+        return 0;
+    g.resize(at + (size_t) nblk);
+    (void) lh_gain_plan_call(&b->rg_cur[(size_t) s], fs, mfn, n, g.data() + at, nblk);
     return 0;
 }
 
@@ -1235,8 +1332,11 @@ lamehip_batch_append(lamehip_batch * b, int s, const short *l, const short *r, i
     }
     if ((rc = batch_stage_reserve(b)) != 0)
         return rc;
+    if ((rc = batch_rg_plan_append(b, "lamehip_batch_append", s, n, false)) != 0)
+        return rc;
     if (b->inc_rs && (rc = batch_rs_plan_append(b, "lamehip_batch_append", s, n, true)) != 0)
         return rc;
+    (void) batch_rg_plan_append(b, "lamehip_batch_append", s, n, true);
     /* pieces of at most half the arena; when the arena or the chunk table is full, what is staged leaves for HBM */
     while (n > 0) {
         int const piece = ((long) n > b->stage_cap / 4) ? (int) (b->stage_cap / 4) : n;
@@ -1324,8 +1424,11 @@ lamehip_batch_append_input(lamehip_batch * b, int s, const void *l, const void *
     }
     if (!batch_append_fits(b, who, s, n))
         return -1;
+    if ((rc = batch_rg_plan_append(b, who, s, n, false)) != 0)
+        return rc;
     if (b->inc_rs && (rc = batch_rs_plan_append(b, who, s, n, true)) != 0)
         return rc;
+    (void) batch_rg_plan_append(b, who, s, n, true);
     long const esz = b->esz;
     bool const inter = (stride == 2 && !one_plane && (const char *) r == (const char *) l + esz);
     /* pieces of at most a quarter of the arena's bytes per plane; when the arena or the table is full, what is staged
@@ -1415,8 +1518,11 @@ lamehip_batch_append_input_device(lamehip_batch * b, int s, const void *dl, cons
     }
     if (!batch_append_fits(b, who, s, n))
         return -1;
+    if ((rc = batch_rg_plan_append(b, who, s, n, false)) != 0)
+        return rc;
     if (b->inc_rs && (rc = batch_rs_plan_append(b, who, s, n, true)) != 0)
         return rc;
+    (void) batch_rg_plan_append(b, who, s, n, true);
     LhApSeg & g = b->h_ap.get()[LH_STAGE_SEGS];
     g.l = (unsigned long long) (uintptr_t) dl;
     g.r = (unsigned long long) (uintptr_t) dr;
@@ -1453,6 +1559,13 @@ lamehip_batch_append_device(lamehip_batch * b, const void *dev, long long stream
         if (!batch_append_fits(b, who, s, nsamples[s]))
             return -1;
     }
+    /* (the same for the analysis of a batch that measures ReplayGain round by round: checked, room made, then counted) */
+    for (int s = 0; s < b->B; s++)
+        if (nsamples[s] > 0 && (rc = batch_rg_plan_append(b, who, s, nsamples[s], false)) != 0)
+            return rc;
+    for (int s = 0; s < b->B && !b->inc_rs; s++)
+        if (nsamples[s] > 0)
+            (void) batch_rg_plan_append(b, who, s, nsamples[s], true);
     if (b->inc_rs) {
         /* (the same for the conversion: every stream's call checked and the round's list made large enough, then counted) */
         size_t  ntiles = 0;
@@ -1557,6 +1670,9 @@ batch_tiles_done(lamehip_batch * b)
         b->rs_conv[(size_t) s] = b->rs_cur[(size_t) s].fed;
 }
 
+static int batch_gain_round(lamehip_batch * b);
+static void batch_gain_round_done(lamehip_batch * b, int end);
+
 /* encode frames [done, upto[s]) of every stream and pack them into pending[]; `end' marks the
  * streams' last frames (flush) */
 static int
@@ -1589,10 +1705,14 @@ batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
     /* (the round's conversion, also when no frame is complete yet: the floats are there when one is) */
     if (b->inc_rs && (rc = batch_tiles_launch(b)) != 0)
         return rc;
+    /* (the round's ReplayGain analysis: behind them, the samples are in the pool the kernels read) */
+    if (b->inc_rg && (rc = batch_gain_round(b)) != 0)
+        return rc;
     if (total == 0) {
         HIPCHK(hipStreamSynchronize(b->stream));
         batch_append_time(b);
         batch_tiles_done(b);
+        batch_gain_round_done(b, end);
         return 0;
     }
     {
@@ -1610,6 +1730,7 @@ batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
     HIPCHK(hipStreamSynchronize(b->stream));
     batch_append_time(b);
     batch_tiles_done(b);
+    batch_gain_round_done(b, end);
     for (int s = 0; s < b->B; s++) {
         LhBitstream *bs = &b->packer[(size_t) s];
         std::vector < unsigned char >&out = b->pending[(size_t) s];
@@ -1670,14 +1791,20 @@ batch_rs_plan_finish(lamehip_batch * b)
     size_t const tiles_before = b->h_tiles.size();
     std::vector < LhRsCursor > end;
     std::vector < int >padding;
+    std::vector < size_t > rg_before;   /* (ReplayGain round by round: the flush's made counts join the last round's blocks) */
     try {
         end = b->rs_cur;
         padding.assign((size_t) b->B, 0);
+        for (const std::vector < int >&g:b->rg_blk)
+            rg_before.push_back(g.size());
         for (int s = 0; s < b->B; s++) {
             LhRsCursor c = b->rs_cur[(size_t) s];
             int const nblk = lh_rs_plan_flush(b->rs, fs, mfn, &c, nullptr, 0, &padding[(size_t) s]);
             b->rs_blk.resize((size_t) nblk);
             (void) lh_rs_plan_flush(b->rs, fs, mfn, &end[(size_t) s], b->rs_blk.data(), nblk, &padding[(size_t) s]);
+            for (const LhRsBlock & k:b->rs_blk)
+                if (b->inc_rg && k.made > 0)
+                    b->rg_blk[(size_t) s].push_back(k.made);
             for (const LhRsBlock & k:b->rs_blk) {
                 size_t const at = b->h_tiles.size();
                 b->h_tiles.resize(at + (size_t) lh_rs_block_tiles(b->rs, &k, s, nullptr, 0));
@@ -1687,6 +1814,8 @@ batch_rs_plan_finish(lamehip_batch * b)
     }
     catch(const std::bad_alloc &) {
         b->h_tiles.resize(tiles_before);
+        for (size_t s = 0; s < rg_before.size(); s++)
+            b->rg_blk[s].resize(rg_before[s]);
         snprintf(g_err, sizeof(g_err), "lamehip_batch_finish: out of memory (conversion plan)");
         return LAMEHIP_ERR_DEVICE;
     }
@@ -1696,6 +1825,35 @@ batch_rs_plan_finish(lamehip_batch * b)
         b->len[(size_t) s] = (long) end[(size_t) s].fed;
         b->nframes[(size_t) s] = end[(size_t) s].frames;
         b->padding[(size_t) s] = padding[(size_t) s];
+    }
+    return 0;
+}
+
+/* A batch that measures ReplayGain round by round and does not convert, at its end: every stream's flush as the analysis
+ * hears it (lh_gain_plan_flush from the stream's cursor) joins the last round's blocks.  Every append made sure it is not too
+ * long.  An allocation failure returns LAMEHIP_ERR_DEVICE with the batch as it was. */
+static int
+batch_rg_plan_finish(lamehip_batch * b)
+{
+    int const fs = fs_of(b->cfg), mfn = mfn_of(b->cfg);
+    try {
+        for (int s = 0; s < b->B; s++) {
+            LhGainCursor c = b->rg_cur[(size_t) s];
+            std::vector < int >&g = b->rg_blk[(size_t) s];
+            g.reserve(g.size() + (size_t) lh_gain_plan_flush(&c, fs, mfn, nullptr, 0));
+        }
+    }
+    catch(const std::bad_alloc &) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_finish: out of memory (gain plan)");
+        return LAMEHIP_ERR_DEVICE;
+    }
+    for (int s = 0; s < b->B; s++) {
+        LhGainCursor c = b->rg_cur[(size_t) s];
+        std::vector < int >&g = b->rg_blk[(size_t) s];
+        size_t const at = g.size();
+        int const nblk = lh_gain_plan_flush(&c, fs, mfn, nullptr, 0);
+        g.resize(at + (size_t) nblk);
+        (void) lh_gain_plan_flush(&b->rg_cur[(size_t) s], fs, mfn, g.data() + at, nblk);
     }
     return 0;
 }
@@ -1729,6 +1887,8 @@ lamehip_batch_finish(lamehip_batch * b)
         for (int s = 0; s < b->B; s++)
             upto[(size_t) s] = b->nframes[(size_t) s];
     }
+    if (b->inc_rg && !b->inc_rs && (rc = batch_rg_plan_finish(b)) != 0)
+        return rc;
     for (int s = 0; s < b->B && !b->inc_rs; s++) {
         long const len = b->fed[(size_t) s] + b->staged[(size_t) s];
         b->len[(size_t) s] = len;
@@ -1805,6 +1965,9 @@ lamehip_batch_reset(lamehip_batch * b)
             lh_rs_cursor_init(&c);
         b->rs_conv.assign(b->rs_conv.size(), 0);
         b->h_tiles.clear();
+        /* (... that measures ReplayGain round by round: every stream's analysis likewise, the carry in HBM included) */
+        if (batch_gain_restart(b) != 0)
+            return LAMEHIP_ERR_DEVICE;
     }
     /* every gain is forgotten, and every stream with it: the next encode measures all of them again */
     b->rg_measured = 0;
@@ -1956,6 +2119,32 @@ batch_gain_fetch(lamehip_batch * b)
     return 0;
 }
 
+/* what a launch over h_rg_streams needs besides its streams */
+static int
+batch_gain_params(const lamehip_batch * b, LhGainParams * p)
+{
+    LhReplayGain probe;         /* (only for the row of the filter tables) */
+    memset(p, 0, sizeof(*p));
+    if (lh_rg_start(&probe, b->cfg.samplerate) != 0)
+        return -1;
+    memcpy(p->ky, lh_rg_yule[probe.rate_index], sizeof(p->ky));
+    memcpy(p->kb, lh_rg_butter[probe.rate_index], sizeof(p->kb));
+    p->m = lh_rs_matrix(b->cfg.pcm_scale, b->cfg.pcm_mix, b->cfg.pcm_scale_r);
+    p->cap = batch_reads_floats(b) ? b->capf : b->cap;
+    p->window = (int) batch_gain_window(b);
+    p->fs = fs_of(b->cfg);
+    p->channels = b->cfg.channels;
+    p->one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
+    {
+        /* the mapping of the first filter's feedback, by the size of the launch (LH_GN_TAPS_BELOW: the faster one either side);
+         * LAMEHIP_GAIN_LANES=0 / 1 (measurement aid, tools/replaygain_bench.py) forces the taps across the lanes of a row / the
+         * feedback in lanes 0 and 1 -- the same sums either way, so a batch measured round by round may change it every round */
+        const char *e = getenv("LAMEHIP_GAIN_LANES");
+        p->taps = e ? atoi(e) != 1 : (int) b->h_rg_streams.size() < LH_GN_TAPS_BELOW;
+    }
+    return 0;
+}
+
 /* The streams declared since their last analysis go through the gain kernel, on the batch's stream: the host plans --
  * which blocks the handle API would have handed to lh_rg_block, from the lengths alone --, the plan travels, one launch. */
 static int
@@ -2047,25 +2236,8 @@ batch_gain_launch(lamehip_batch * b)
     HIPCHK(hipMemcpyAsync(b->d_rg_streams.get(), b->h_rg_streams.data(), b->h_rg_streams.size() * sizeof(LhGainStream), hipMemcpyHostToDevice,
                           b->stream));
     LhGainParams p;
-    LhReplayGain probe;         /* (only for the row of the filter tables) */
-    memset(&p, 0, sizeof(p));
-    if (lh_rg_start(&probe, b->cfg.samplerate) != 0)
+    if (batch_gain_params(b, &p) != 0)
         return -1;
-    memcpy(p.ky, lh_rg_yule[probe.rate_index], sizeof(p.ky));
-    memcpy(p.kb, lh_rg_butter[probe.rate_index], sizeof(p.kb));
-    p.m = lh_rs_matrix(b->cfg.pcm_scale, b->cfg.pcm_mix, b->cfg.pcm_scale_r);
-    p.cap = batch_reads_floats(b) ? b->capf : b->cap;
-    p.window = (int) W;
-    p.fs = fs;
-    p.channels = b->cfg.channels;
-    p.one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
-    {
-        /* the mapping of the first filter's feedback, by the size of the launch (LH_GN_TAPS_BELOW: the faster one either side);
-         * LAMEHIP_GAIN_LANES=0 / 1 (measurement aid, tools/replaygain_bench.py) forces the taps across the lanes of a row / the
-         * feedback in lanes 0 and 1 -- the same sums either way */
-        const char *e = getenv("LAMEHIP_GAIN_LANES");
-        p.taps = e ? atoi(e) != 1 : (int) b->h_rg_streams.size() < LH_GN_TAPS_BELOW;
-    }
     HIPCHK(hipEventRecord(b->ev_rg[0], b->stream));
     int const rc = lh_launch_gain(batch_reads_floats(b), &p, b->d_rg_streams.get(), (int) b->h_rg_streams.size(),
                                   b->dev_rs ? b->d_rg_trunk.get() : nullptr, b->d_rg_tails.get(),
@@ -2080,6 +2252,95 @@ batch_gain_launch(lamehip_batch * b)
     b->rg_ran = 1;
     b->rg_pending = 1;
     return 0;
+}
+
+/* A round of a batch that measures ReplayGain round by round (lamehip_batch_encode_available / _finish): the streams with
+ * blocks planned since the last round go through lh_gain_resume_kernel, ONE launch on the batch's stream between ev_rg[0] and
+ * ev_rg[1], behind the append and conversion launches -- every sample the blocks cover is in the pool the kernels read,
+ * counted in fed[] (in rs_cur[].fed where the batch converts), and what lies beyond is generated zeros, the flush's --;
+ * the round's window sums follow the launch home.  A stream without blocks is not part of the launch: its carry stays. */
+static int
+batch_gain_round(lamehip_batch * b)
+{
+    long const W = batch_gain_window(b);
+    long long wins = 0;
+    b->rg_ran = 0;
+    b->h_rg_streams.clear();
+    b->h_rg_tails.clear();
+    for (int s = 0; s < b->B; s++) {
+        std::vector < int >const &g = b->rg_blk[(size_t) s];
+        if (g.empty())
+            continue;
+        LhGainStream d;
+        long long const heard = b->rg_heard[(size_t) s];
+        long long total = 0;
+        for (int k:g)
+            total += k;
+        memset(&d, 0, sizeof(d));
+        d.n = b->inc_rs ? b->rs_cur[(size_t) s].fed : (long long) b->fed[(size_t) s];
+        d.win_at = wins;
+        d.total = (int) total;
+        d.stream = s;
+        d.tail_at = (int) b->h_rg_tails.size();
+        d.ntail = (int) g.size();
+        b->h_rg_tails.insert(b->h_rg_tails.end(), g.begin(), g.end());
+        wins += (heard + total) / W - heard / W;
+        b->h_rg_streams.push_back(d);
+    }
+    if (b->h_rg_streams.empty())
+        return 0;
+    /* (nothing of an earlier round is in flight: a round ends with a wait) */
+    HIPCHK(b->d_rg_tails.reserve(b->h_rg_tails.size() + 1, b->h_rg_tails.size(), b->stream));
+    HIPCHK(b->d_rg_pairs.reserve((size_t) (2 * wins + 2), (size_t) (2 * wins), b->stream));
+    b->h_rg_round.resize((size_t) (2 * wins));
+    HIPCHK(hipMemcpyAsync(b->d_rg_tails.get(), b->h_rg_tails.data(), b->h_rg_tails.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemcpyAsync(b->d_rg_streams.get(), b->h_rg_streams.data(), b->h_rg_streams.size() * sizeof(LhGainStream), hipMemcpyHostToDevice,
+                          b->stream));
+    LhGainParams p;
+    if (batch_gain_params(b, &p) != 0)
+        return -1;
+    HIPCHK(hipEventRecord(b->ev_rg[0], b->stream));
+    int const rc = lh_launch_gain_resume(batch_reads_floats(b), &p, b->d_rg_streams.get(), (int) b->h_rg_streams.size(), b->d_rg_tails.get(),
+                                         batch_reads_floats(b) ? (const void *) b->d_pcmf.get() : (const void *) b->d_pcm.get(),
+                                         b->d_rg_pairs.get(), b->d_rg_carry.get(), (void *) (hipStream_t) b->stream);
+    if (rc)
+        return set_err("gain launch", (hipError_t) rc);
+    HIPCHK(hipEventRecord(b->ev_rg[1], b->stream));
+    if (wins > 0)
+        HIPCHK(hipMemcpyAsync(b->h_rg_round.data(), b->d_rg_pairs.get(), b->h_rg_round.size() * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    b->rg_ran = 1;
+    return 0;
+}
+
+/* behind the round's wait: the launch's time (lamehip_batch_last_gain_ms), every stream's new windows join its list, the
+ * blocks are done with; end: the flush was part of the round, the gains are made of the windows (lh_replaygain.c) */
+static void
+batch_gain_round_done(lamehip_batch * b, int end)
+{
+    long const W = batch_gain_window(b);
+    if (!b->inc_rg)
+        return;
+    b->rg_ms = 0;
+    if (b->rg_ran) {
+        if (hipEventElapsedTime(&b->rg_ms, b->ev_rg[0], b->ev_rg[1]) != hipSuccess) {
+            (void) hipGetLastError();
+            b->rg_ms = 0;
+        }
+        for (const LhGainStream & d:b->h_rg_streams) {
+            long long &heard = b->rg_heard[(size_t) d.stream];
+            long long const nw = (heard + d.total) / W - heard / W;
+            std::vector < double >&w = b->rg_win[(size_t) d.stream];
+            w.insert(w.end(), b->h_rg_round.begin() + 2 * d.win_at, b->h_rg_round.begin() + 2 * (d.win_at + nw));
+            heard += d.total;
+            b->rg_blk[(size_t) d.stream].clear();
+        }
+        b->h_rg_streams.clear();
+    }
+    if (end) {
+        for (int s = 0; s < b->B; s++)
+            b->rg_tenths[(size_t) s] = lh_gain_from_windows(b->rg_win[(size_t) s].data(), (long) (b->rg_win[(size_t) s].size() / 2), W);
+        b->rg_closed = 1;
+    }
 }
 
 /* the tag of stream s carries its gain when the batch measures it */
@@ -2111,6 +2372,7 @@ lamehip_batch_set_replaygain(lamehip_batch * b, int on)
     }
     if (!on || b->rg_on) {
         b->rg_on = on != 0 && b->rg_on;
+        b->inc_rg = b->inc_rg && b->rg_on;      /* (round by round is this analysis' too) */
         return 0;
     }
     /* everything new first: a failure leaves the batch as it was */
@@ -2137,11 +2399,102 @@ lamehip_batch_set_replaygain(lamehip_batch * b, int on)
     return 0;
 }
 
+/* ReplayGain round by round, for an incremental batch: once lamehip_batch_append (or one of its siblings) feeds the batch,
+ * every append is a call of the reference entry point the batch's sample type is named after, made with
+ * lame_set_findReplayGain(1); every lamehip_batch_encode_available and lamehip_batch_finish analyses what was appended since
+ * the last round -- lamehip_batch_finish the flush as well --, lamehip_batch_get_gain_windows returns the windows finished so
+ * far after any round, and lamehip_batch_radio_gain, after lamehip_batch_finish, what lame_get_RadioGain returns on a handle
+ * fed the same calls.  Until the first append the batch measures whole streams, as after lamehip_batch_set_replaygain(b, 1).
+ * Only before any PCM is handed over; a batch that converts the rate needs lamehip_batch_set_incremental_resampling first;
+ * not for a batch that packs on the device.  on = 0 puts the batch back as it was. */
+extern "C" int
+lamehip_batch_set_incremental_replaygain(lamehip_batch * b, int on)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b)
+        return -1;
+    if (b->pcm_given || b->encoded || b->incremental) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_incremental_replaygain: only before any PCM is handed over");
+        return -1;
+    }
+    if (!on || b->inc_rg) {
+        if (!on && b->inc_rg) {
+            b->inc_rg = 0;
+            b->rg_on = b->rg_was_on;
+        }
+        return 0;
+    }
+    if (b->dev_pack) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_incremental_replaygain: not for a batch that packs on the device "
+                 "(lamehip_batch_set_device_packing), which incremental use does not");
+        return -1;
+    }
+    if (b->rate_in && !b->inc_rs) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_incremental_replaygain: this batch converts the sample rate, "
+                 "lamehip_batch_set_incremental_resampling first (the analysis follows the conversion's calls)");
+        return -1;
+    }
+    /* everything new first: a failure leaves the batch as it was */
+    int const was_on = b->rg_on;
+    LhDevBuf < LhGainCarry > carry;
+    std::vector < LhGainCursor > cur;
+    std::vector < std::vector < int > >blk;
+    std::vector < long long >heard;
+    hipError_t e = carry.alloc((size_t) b->B);
+    if (e == hipSuccess)
+        e = hipMemset(carry.get(), 0, (size_t) b->B * sizeof(LhGainCarry));
+    try {
+        LhGainCursor first;
+        lh_gain_cursor_init(&first);
+        cur.assign((size_t) b->B, first);
+        blk.assign((size_t) b->B, std::vector < int >());
+        heard.assign((size_t) b->B, 0);
+    }
+    catch(const std::bad_alloc &) {
+        e = hipErrorOutOfMemory;
+    }
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        return set_err("lamehip_batch_set_incremental_replaygain: allocation", e);
+    }
+    if (!was_on) {
+        int const rc = lamehip_batch_set_replaygain(b, 1);      /* (the launch's records, the events, the lists of windows) */
+        if (rc != 0)
+            return rc;
+    }
+    b->d_rg_carry = std::move(carry);
+    b->rg_cur = std::move(cur);
+    b->rg_blk = std::move(blk);
+    b->rg_heard = std::move(heard);
+    b->rg_was_on = was_on;
+    b->rg_closed = 0;
+    b->inc_rg_max = LH_GN_MAX_TOTAL;
+    {
+        /* LAMEHIP_INC_RG_MAX=n, looked at here: the appends count the analysis as taking n samples per stream, no more than it
+         * does (test aid: the real limit is beyond any pool a test would allocate) */
+        const char *m = getenv("LAMEHIP_INC_RG_MAX");
+        long long const v = m ? strtoll(m, nullptr, 10) : 0;
+        if (v > 0 && v < b->inc_rg_max)
+            b->inc_rg_max = v;
+    }
+    b->inc_rg = 1;
+    return 0;
+}
+
+/* who: one of the getters; final: it needs the gain, which an incremental batch has after lamehip_batch_finish */
 static int
-batch_gain_ready(lamehip_batch * b, int s, const char *who)
+batch_gain_ready(lamehip_batch * b, int s, const char *who, bool final = false)
 {
     if (!b || s < 0 || s >= b->B)
         return -1;
+    if (b->inc_rg && b->incremental) {
+        if (final && !b->rg_closed) {
+            snprintf(g_err, sizeof(g_err), "%s: an incremental batch's gain exists after lamehip_batch_finish (as lame_get_RadioGain's after "
+                     "lame_encode_flush)", who);
+            return -1;
+        }
+        return 0;               /* (the windows came home with the round) */
+    }
     if (!b->rg_on || !b->rg_measured) {
         snprintf(g_err, sizeof(g_err), "%s: no lamehip_batch_encode with lamehip_batch_set_replaygain on has run", who);
         return -1;
@@ -2155,7 +2508,7 @@ extern "C" int
 lamehip_batch_radio_gain(lamehip_batch * b, int s, int *tenths_db)
 {
     LhDeviceScope const on_device(b ? b->device : -1);
-    int const rc = tenths_db ? batch_gain_ready(b, s, "lamehip_batch_radio_gain") : -1;
+    int const rc = tenths_db ? batch_gain_ready(b, s, "lamehip_batch_radio_gain", true) : -1;
     if (rc)
         return rc;
     *tenths_db = b->rg_tenths[(size_t) s];

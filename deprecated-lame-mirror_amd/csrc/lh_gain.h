@@ -51,14 +51,27 @@
  * ntail); their lengths add up to `total'. */
 typedef struct LhGainStream {
     long long n;                /* samples in the pool's rows: nothing at or beyond is ever read (zeros are generated) */
-    long long win_at;           /* the stream's first window in the launch's output: total / window pairs from there */
-    int     total;              /* samples the analysis hears: n and the flush's zeros */
+    long long win_at;           /* the stream's first window in the launch's output: total / window pairs from there (a
+                                 * round: the windows that end in it) */
+    int     total;              /* samples the analysis hears: n and the flush's zeros (a round: the round's blocks alone) */
     int     stream;             /* row pair of the pool */
     int     ntrunk;
     int     tail_at;
     int     ntail;
     int     pad_;
 } LhGainStream;
+
+/* What a stream of an incremental batch carries from round to round (lh_gain_resume_kernel; one record per stream, zeroed
+ * = before the stream's first sample): per channel the last ten inputs behind the PCM matrix, the last ten outputs of the
+ * first filter and the last two of the second, oldest first -- LhReplayGain's hist_in / hist_mid / hist_out[8..9] --, the
+ * open window's sums, the samples heard and the windows finished so far.  A round ends at a block's end, so no piece's sum
+ * is open between rounds.  Mono: channel 0 alone is kept, rsum = lsum. */
+typedef struct LhGainCarry {
+    float   x[2][LH_GN_ORDER], mid[2][LH_GN_ORDER], out[2][2];
+    double  lsum, rsum;
+    long long heard;
+    long long windows;
+} LhGainCarry;
 
 /* what a launch needs besides its streams */
 typedef struct LhGainParams {

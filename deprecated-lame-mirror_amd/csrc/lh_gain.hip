@@ -21,7 +21,24 @@
  *   G  lanes 0 and 1 add the terms up in order: into the piece's sum, that into the window's, and store a finished
  *      window.
  * The blocks come from the host's plan (lh_gain.h): the wave walks them as it goes.  Only wave-level synchronisation;
- * the LH_GN_WAVES waves of a workgroup share nothing.
+ * the LH_GN_WAVES waves of a workgroup share nothing (4 KB of LDS each, 16 KB per workgroup, in either kernel).
+ *
+ * The kernels' text lies in lh_gain_stream.h and is compiled twice: as lh_gain_kernel (GN_RESUME 0), which the compiler
+ * turns into the instructions it made of it before there was a second kernel, and as lh_gain_resume_kernel (GN_RESUME 1),
+ * the same text for an incremental batch: a launch is a ROUND -- what was appended to a stream since the last round, as
+ * the blocks the calls made of it -- and what a stream carries from round
+ * to round lies in its LhGainCarry (lh_gain.h).  Positions are counted from the round's start, `base' = carry.heard samples
+ * into the stream, so the ring's slots and the halves of mid / out (at & LH_GN_RUN) are addressed as in a whole stream
+ * whatever base is: the carry's ten inputs, ten first-filter outputs and two second-filter outputs go into the ring's slots
+ * for positions -10 .. -1, and both mappings of C take their history from there -- lanes 0 to 9 of rows 0 and 1, or q[] --,
+ * which keeps them bit-equal to each other and lets the host choose the mapping anew every round.  Only the windows are
+ * absolute: they end at multiples of W of the samples heard.
+ * INVARIANT the resumed kernel relies on: a round ends at a block's end.  So no piece sum is open at a round's boundary
+ * (only the window's sums are carried), a group of four squares never reaches back into the round before, and the block
+ * cursor restarts at 0 with every round.  The last run's lanes beyond the round's end have run the filters on zeros: the
+ * carry is therefore read back from the ring at the round's end, not from the registers, and stored with ordinary
+ * stores.  The inputs are kept in the carry rather than read from the pool again: the ring holds them already, behind the
+ * PCM matrix, and a float pool's rows need no second look.
  * Every rounding is named (lh_gain.h).  Built with -ffp-contract=off like every object of the library, and without
  * flushing subnormals: the first filter's output is subnormal within a thousand samples of silence and stays so.
  */
@@ -86,195 +103,13 @@ gain_yule_feedback(const float (&q)[LH_GN_ORDER], const float *ky)
     return LH_GN_DADD(LH_GN_DADD(LH_GN_DADD(LH_GN_DADD(x1, x5), x9), xD), xH);
 }
 
-/* grid: x = LH_GN_WAVES entries of `streams' */
-template < typename T, int TAPS >
-#ifndef LH_EMU
-__global__ void __launch_bounds__(LH_GN_NT)
-#else
-void
-#endif
-lh_gain_kernel(LhGainParams p, const LhGainStream * streams, int nstreams, const int *trunk, const int *tails, const T * pool,
-               double *pairs)
-{
-    __shared__ LhGainLds lds[LH_GN_WAVES];
-    int const lane = lh_lane(), wave = lh_wave_id();
-    int const si = (int) blockIdx.x * LH_GN_WAVES + wave;
-    if (si >= nstreams)
-        return;                 /* (the whole wave: nothing below waits for another wave) */
-    LhGainLds & L = lds[wave];
-    LhGainStream const sd = streams[si];
-    int const nch = p.channels == 1 ? 1 : 2, W = p.window;
-    int const nblk = sd.ntrunk + sd.ntail;
-    const T *row_l = pool + (size_t) sd.stream * 2 * (size_t) p.cap, *row_r = row_l + p.cap;
-    double *out = pairs + 2 * sd.win_at;
-    /* what lanes 0 and 1 carry from run to run: the filters' histories and the sums; every lane: the block cursor */
-    float   q[LH_GN_ORDER], o1 = 0.0f, o2 = 0.0f;
-    double  sum = 0.0, wsum = 0.0;
-    int     wins = 0;
-    int     blk = 0, blk_at = 0, blk_len = nblk > 0 ? gain_block_len(sd, p.fs, trunk, tails, 0) : 0;
-    /* TAPS: lane r < 10 of a row of 16 holds the first filter's output 10 - r samples back and its feedback tap; rows 0 and 1
-     * are the channels (rows 2 and 3 shadow them and store nothing) */
-    int const tap = lane & 15, tap_ch = (lane >> 4) & 1;
-    bool const tap_writer = tap == 8 && (lane >> 4) < nch;
-    float   kt = 0.0f, h = 0.0f;
-#pragma unroll
-    for (int j = 0; j < LH_GN_ORDER; ++j) {
-        q[j] = 0.0f;
-        if (tap == j)
-            kt = p.ky[11 + j];
-    }
-    for (int c = 0; c < 2; ++c)
-        for (int k = lane; k < LH_GN_RING; k += 64)
-            L.x[c][k] = L.mid[c][k] = L.out[c][k] = 0.0f;
-    LH_WAVE_SYNC();
-    for (int at = 0; at < sd.total; at += LH_GN_RUN) {
-        int const pos = at + lane, slot = pos & (LH_GN_RING - 1), half = at & LH_GN_RUN;
-        /* A */
-        {
-            float   xl = 0.0f, xr = 0.0f;
-            if (pos < sd.n) {
-                if (sizeof(T) == 2) {
-                    float const sl = (float) row_l[pos], sr = p.one_plane ? sl : (float) row_r[pos];
-                    xl = lh_rs_mix(sl, sr, p.m.m00, p.m.m01);
-                    if (nch == 2)
-                        xr = lh_rs_mix(sl, sr, p.m.m10, p.m.m11);
-                }
-                else {
-                    xl = (float) row_l[pos];
-                    if (nch == 2)
-                        xr = (float) row_r[pos];
-                }
-            }
-            L.x[0][slot] = xl;
-            L.x[1][slot] = xr;
-        }
-        LH_WAVE_SYNC();
-        /* B */
-        for (int c = 0; c < nch; ++c)
-            L.d[c][lane] = gain_yule_forward(L.x[c], pos, p.ky);
-        LH_WAVE_SYNC();
-        /* C */
-        if (TAPS) {
-            /* one instruction stream for both channels: the ten products at once, the pairs (float sums) on the even lanes,
-             * then the ordered double sum walks up the row two lanes at a time -- x1 in lane 0, + x5 in lane 2, + x9, + xD,
-             * + xH in lane 8, which forms the output; the history moves down a lane and takes the output in at lane 9 */
-            const double *s1 = L.d[tap_ch];
-            float  *mid = L.mid[tap_ch] + half;
-#pragma unroll 8
-            for (int i = 0; i < LH_GN_RUN; ++i) {
-                float const pr = LH_GN_FMUL(h, kt);
-                double const x = (double) LH_GN_FADD(pr, lh_row_shl_f32 < 1 > (pr));
-                double  acc = x;
-                acc = LH_GN_DADD(lh_row_shr_f64 < 2 > (acc), x);
-                acc = LH_GN_DADD(lh_row_shr_f64 < 2 > (acc), x);
-                acc = LH_GN_DADD(lh_row_shr_f64 < 2 > (acc), x);
-                acc = LH_GN_DADD(lh_row_shr_f64 < 2 > (acc), x);
-                float const v = LH_GN_NARROW(LH_GN_DSUB(s1[i], acc));
-                if (tap_writer)
-                    mid[i] = v;
-                float const older = lh_row_shl_f32 < 1 > (h), newest = lh_row_shr_f32 < 1 > (v);
-                h = tap == 9 ? newest : older;
-            }
-        }
-        else if (lane < nch) {
-            const double *s1 = L.d[lane];
-            float  *mid = L.mid[lane] + half;
-            for (int i0 = 0; i0 < LH_GN_RUN; i0 += 16) {
-#pragma unroll
-                for (int u = 0; u < 16; ++u) {
-                    float const v = LH_GN_NARROW(LH_GN_DSUB(s1[i0 + u], gain_yule_feedback(q, p.ky)));
-#pragma unroll
-                    for (int j = LH_GN_ORDER - 1; j > 0; --j)
-                        q[j] = q[j - 1];
-                    q[0] = v;
-                    mid[i0 + u] = v;
-                }
-            }
-        }
-        LH_WAVE_SYNC();
-        /* D */
-        for (int c = 0; c < nch; ++c) {
-            const float *m = L.mid[c];
-            /* (three products in one float expression) */
-            L.d[c][lane] = (double) LH_GN_FADD(LH_GN_FADD(LH_GN_FMUL(GN_AT(m, pos, 2), p.kb[0]), LH_GN_FMUL(GN_AT(m, pos, 1), p.kb[2])),
-                                               LH_GN_FMUL(GN_AT(m, pos, 0), p.kb[4]));
-        }
-        LH_WAVE_SYNC();
-        /* E */
-        if (lane < nch) {
-            const double *s1 = L.d[lane];
-            float  *o = L.out[lane] + half;
-#pragma unroll 16
-            for (int i = 0; i < LH_GN_RUN; ++i) {
-                double const s2 = LH_GN_TAP2(o2, p.kb[1], o1, p.kb[3]);
-                float const v = LH_GN_NARROW(LH_GN_DSUB(s1[i], s2));
-                o2 = o1;
-                o1 = v;
-                o[i] = v;
-            }
-        }
-        LH_WAVE_SYNC();
-        /* F */
-        bool const valid = pos < sd.total;
-        int     j = blk, b0 = blk_at, bn = blk_len;
-        while (valid && pos >= b0 + bn && j + 1 < nblk) {
-            b0 += bn;
-            ++j;
-            bn = gain_block_len(sd, p.fs, trunk, tails, j);
-        }
-        int const w0 = (pos / W) * W, in_blk = pos - b0;
-        int     first = b0 + (in_blk >= LH_GN_ORDER ? LH_GN_ORDER : 0), end = b0 + bn;
-        if (w0 > first)
-            first = w0;
-        if (in_blk < LH_GN_ORDER && b0 + LH_GN_ORDER < end)
-            end = b0 + LH_GN_ORDER;
-        if (w0 + W < end)
-            end = w0 + W;
-        int const k = pos - first, head = (end - first) & 3;
-        bool const single = valid && k < head, four = valid && k >= head && ((k - head) & 3) == 3;
-        for (int c = 0; c < nch; ++c) {
-            const float *o = L.out[c];
-            double  t = 0.0;
-            if (single) {
-                double const v = (double) GN_AT(o, pos, 0);
-                t = LH_GN_DMUL(v, v);
-            }
-            else if (four) {
-                float const fa = GN_AT(o, pos, 3), fb = GN_AT(o, pos, 2), fc = GN_AT(o, pos, 1), fd = GN_AT(o, pos, 0);
-                t = LH_GN_DADD(LH_GN_DADD(LH_GN_DADD(LH_GN_TAP(fa, fa), LH_GN_TAP(fb, fb)), LH_GN_TAP(fc, fc)), LH_GN_TAP(fd, fd));
-            }
-            L.d[c][lane] = t;
-        }
-        uint64_t const m_term = lh_ballot(single || four), m_last = lh_ballot(valid && pos == end - 1);
-        uint64_t const m_win = lh_ballot(valid && pos == w0 + W - 1);
-        LH_WAVE_SYNC();
-        /* G */
-        if (lane < nch) {
-            uint64_t m = m_term | m_last;
-            while (m) {
-                int const i = lh_ffs64(m);
-                m &= m - 1;
-                if ((m_term >> i) & 1)
-                    sum = LH_GN_DADD(sum, L.d[lane][i]);
-                if ((m_last >> i) & 1) {
-                    wsum = LH_GN_DADD(wsum, sum);
-                    sum = 0.0;
-                    if ((m_win >> i) & 1) {
-                        out[2 * (long long) wins + lane] = wsum;
-                        if (nch == 1)
-                            out[2 * (long long) wins + 1] = wsum;
-                        wsum = 0.0;
-                        ++wins;
-                    }
-                }
-            }
-        }
-        blk = (int) lh_bcast_u32((uint32_t) j, 63);
-        blk_at = (int) lh_bcast_u32((uint32_t) b0, 63);
-        blk_len = (int) lh_bcast_u32((uint32_t) bn, 63);
-        LH_WAVE_SYNC();
-    }
-}
+/* the kernels' text, compiled twice (lh_gain_stream.h) */
+#define GN_RESUME 0
+#include "lh_gain_stream.h"
+#undef GN_RESUME
+#define GN_RESUME 1
+#include "lh_gain_stream.h"
+#undef GN_RESUME
 
 #ifndef LH_EMU
 /* nstreams entries of `streams' (device), `pool' s16 or -- floats != 0 -- float.  Returns a hipError_t. */
@@ -299,6 +134,30 @@ lh_launch_gain(int floats, const LhGainParams * p, const LhGainStream * streams,
         GN_LAUNCH(int16_t, 0);
     return (int) hipGetLastError();
 }
+
+/* a round of an incremental batch: nstreams entries of `streams' (device) -- total and tails the round's, ntrunk 0 --, from
+ * and to `carry' (device, one record per stream of the batch).  Returns a hipError_t. */
+extern "C" int
+lh_launch_gain_resume(int floats, const LhGainParams * p, const LhGainStream * streams, int nstreams, const int *tails, const void *pool,
+                      double *pairs, LhGainCarry * carry, void *stream)
+{
+    if (nstreams <= 0)
+        return 0;
+    if (p->window < 1 || p->fs < 1 || !carry)
+        return (int) hipErrorInvalidValue;
+    dim3 const grid((unsigned) ((nstreams + LH_GN_WAVES - 1) / LH_GN_WAVES)), block(LH_GN_NT);
+#define GN_RESUME(T, TAPS) hipLaunchKernelGGL((lh_gain_resume_kernel < T, TAPS >), grid, block, 0, (hipStream_t) stream, *p, streams, \
+                                             nstreams, tails, (const T *) pool, pairs, carry)
+    if (floats && p->taps)
+        GN_RESUME(float, 1);
+    else if (floats)
+        GN_RESUME(float, 0);
+    else if (p->taps)
+        GN_RESUME(int16_t, 1);
+    else
+        GN_RESUME(int16_t, 0);
+    return (int) hipGetLastError();
+}
 #else
 extern "C" int
 lh_emu_gain(int floats, const LhGainParams * params, const LhGainStream * streams, int nstreams, const int *trunk, const int *tails,
@@ -319,6 +178,30 @@ lh_emu_gain(int floats, const LhGainParams * params, const LhGainStream * stream
                    lh_gain_kernel < int16_t, 1 > (p, streams, nstreams, trunk, tails, (const int16_t *) pool, pairs);
                else
                    lh_gain_kernel < int16_t, 0 > (p, streams, nstreams, trunk, tails, (const int16_t *) pool, pairs);
+               }
+    );
+    return 0;
+}
+
+extern "C" int
+lh_emu_gain_resume(int floats, const LhGainParams * params, const LhGainStream * streams, int nstreams, const int *tails, const void *pool,
+                   double *pairs, LhGainCarry * carry)
+{
+    LhGainParams const p = *params;
+    hipemu_dim3 grid = { (unsigned) ((nstreams + LH_GN_WAVES - 1) / LH_GN_WAVES), 1, 1 }, block = { LH_GN_NT, 1, 1 };
+    if (nstreams <= 0)
+        return 0;
+    if (p.window < 1 || p.fs < 1 || !carry)
+        return -1;
+    hipemu_run(grid, block,[=] () {
+               if (floats && p.taps)
+                   lh_gain_resume_kernel < float, 1 > (p, streams, nstreams, tails, (const float *) pool, pairs, carry);
+               else if (floats)
+                   lh_gain_resume_kernel < float, 0 > (p, streams, nstreams, tails, (const float *) pool, pairs, carry);
+               else if (p.taps)
+                   lh_gain_resume_kernel < int16_t, 1 > (p, streams, nstreams, tails, (const int16_t *) pool, pairs, carry);
+               else
+                   lh_gain_resume_kernel < int16_t, 0 > (p, streams, nstreams, tails, (const int16_t *) pool, pairs, carry);
                }
     );
     return 0;

@@ -241,6 +241,16 @@ int     lh_gain_from_windows(const double *pairs, long nwin, long window);
 /* a batch stream's analysis as a plan -- the blocks lame_encode_buffer would hand to lh_rg_block, from the stream's length
  * alone; rs == NULL: no rate conversion -- and the plan evaluated on host samples (lh_gain.hip's twin) */
 int     lh_gain_plan(const LhResampler * rs, int fs, int mfn, long n, int *blocks, int cap, long *total);
+/* the same for a stream fed call by call (an incremental batch without rate conversion): a cursor per stream -- samples the
+ * analysis has heard, and the samples fed / frames out as lame_encode_flush counts them --, one call of m samples, the flush */
+typedef struct LhGainCursor {
+    long long heard;
+    long long fed;
+    long    frames;
+} LhGainCursor;
+void    lh_gain_cursor_init(LhGainCursor * c);
+int     lh_gain_plan_call(LhGainCursor * c, int fs, int mfn, int m, int *blocks, int cap);
+int     lh_gain_plan_flush(LhGainCursor * c, int fs, int mfn, int *blocks, int cap);
 long    lh_gain_eval_host(int samplerate, int channels, const int *blocks, int nblocks, const float *l, const float *r, long n,
                           double *pairs, long cap, int *tenths);
 

@@ -208,11 +208,71 @@ lh_gain_from_windows(const double *pairs, long nwin, long window)
     return tenths;
 }
 
+/* ---- the analysis of a stream fed call by call (an incremental batch), from a cursor of its own ----
+ *
+ * Without rate conversion lame_encode_buffer hands the analysis a call's samples as they come, in blocks of at most one
+ * frame counted from the call's start (reference lame.c:1713-1720): lh_gain_plan_call is one call of m samples at the
+ * cursor -- fs, fs, ..., the remainder; none for m == 0 --, lh_gain_plan_flush the bunches of zeros lame_encode_flush feeds
+ * until the frames still owed are out (lh_api.cpp).  Both return the number of blocks, write only the first `cap'
+ * (blocks == NULL: none) and advance the cursor; -1 for arguments no stream has.  No sample is looked at.  (A batch that
+ * converts the rate takes the made counts of lh_rs_plan_call / lh_rs_plan_flush instead: lh_batch.cpp.) */
+void
+lh_gain_cursor_init(LhGainCursor * c)
+{
+    c->heard = c->fed = 0;
+    c->frames = 0;
+}
+
+int
+lh_gain_plan_call(LhGainCursor * c, int fs, int mfn, int m, int *blocks, int cap)
+{
+    int     k = 0, at;
+    if (!c || fs < 1 || m < 0)
+        return -1;
+    for (at = 0; at < m; at += fs) {
+        if (blocks && k < cap)
+            blocks[k] = m - at > fs ? fs : m - at;
+        k++;
+    }
+    c->heard += m;
+    c->fed += m;
+    if (LH_MF_START + c->fed >= mfn)
+        c->frames = (long) ((LH_MF_START + c->fed - mfn) / fs + 1);
+    return k;
+}
+
+int
+lh_gain_plan_flush(LhGainCursor * c, int fs, int mfn, int *blocks, int cap)
+{
+    int     k = 0, owed, padding, frames_left;
+    if (!c || fs < 1)
+        return -1;
+    owed = (int) (576 + c->fed - (long long) fs * c->frames);
+    padding = fs - (owed % fs);
+    if (padding < 576)
+        padding += fs;
+    frames_left = (owed + padding) / fs;
+    while (frames_left > 0) {
+        int     bunch = mfn - (int) (LH_MF_START + c->fed - (long long) fs * c->frames);
+        bunch = bunch > 1152 ? 1152 : (bunch < 1 ? 1 : bunch);
+        if (blocks && k < cap)
+            blocks[k] = bunch;
+        k++;
+        c->fed += bunch;
+        c->heard += bunch;
+        if (LH_MF_START + c->fed - (long long) fs * c->frames >= mfn) {
+            c->frames++;
+            frames_left--;
+        }
+    }
+    return k;
+}
+
 /* ---- the analysis of a batch's stream as a plan (the device kernel's input, lh_gain.hip) and its host evaluation ----
  *
  * lh_gain_plan: the blocks the handle API hands to lh_rg_block for a stream of n input samples fed `fs' samples per
  * lame_encode_buffer call and flushed, from the length alone.  rs == NULL, no rate conversion: fs samples from position 0
- * on, the remainder, then the flush's bunches of zeros (lame_encode_flush, lh_api.cpp).  Else the made counts of the
+ * on, the remainder, then the flush's bunches of zeros (lh_gain_plan_call per call, lh_gain_plan_flush).  Else the made counts of the
  * stream's conversion plan (lh_rs_plan: trunk, then tail, flush blocks included).  Returns the number of blocks -- only
  * the first `cap' are written --, or -1; *total = the samples they add up to. */
 int
@@ -246,32 +306,22 @@ lh_gain_plan(const LhResampler * rs, int fs, int mfn, long n, int *blocks, int c
             free(b);
     }
     else {
-        long    fed, at;
-        long    frames = (n > 0 && LH_MF_START + n >= mfn) ? (LH_MF_START + n - mfn) / fs + 1 : 0;
-        int const owed = (int) (576 + n - (long) fs * frames);
-        int     padding = fs - (owed % fs), frames_left;
+        /* a frame's worth per call, then the flush: the call plan's special case */
+        LhGainCursor c;
+        long    at;
+        int     nb;
+        lh_gain_cursor_init(&c);
         for (at = 0; at < n; at += fs) {
-            if (k < cap)
-                blocks[k] = (int) (n - at > fs ? fs : n - at);
-            k++;
+            nb = lh_gain_plan_call(&c, fs, mfn, (int) (n - at > fs ? fs : n - at), k < cap ? blocks + k : NULL, k < cap ? cap - k : 0);
+            if (nb < 0)
+                return -1;
+            k += nb;
         }
-        sum = fed = n;
-        if (padding < 576)
-            padding += fs;
-        frames_left = (owed + padding) / fs;
-        while (frames_left > 0) {
-            int     bunch = mfn - (int) (LH_MF_START + fed - (long) fs * frames);
-            bunch = bunch > 1152 ? 1152 : (bunch < 1 ? 1 : bunch);
-            if (k < cap)
-                blocks[k] = bunch;
-            k++;
-            fed += bunch;
-            sum += bunch;
-            if (LH_MF_START + fed - (long) fs * frames >= mfn) {
-                frames++;
-                frames_left--;
-            }
-        }
+        nb = lh_gain_plan_flush(&c, fs, mfn, k < cap ? blocks + k : NULL, k < cap ? cap - k : 0);
+        if (nb < 0)
+            return -1;
+        k += nb;
+        sum = (long) c.heard;
     }
     if (total)
         *total = sum;

@@ -279,6 +279,15 @@ class Batch:
         if rc:
             raise RuntimeError("lamehip_batch_set_replaygain failed (%d): %s" % (rc, last_error()))
 
+    def set_incremental_replaygain(self, on=True):
+        """ReplayGain of an incremental batch: every append*() is a call of the reference made with findReplayGain, every
+        encode_available() / finish() analyses what was appended since the last round on the device; gain_windows() after any
+        round, radio_gain() after finish().  Before any PCM; a converting batch needs set_incremental_resampling() first."""
+        self.lib.lamehip_batch_set_incremental_replaygain.argtypes = [C.c_void_p, C.c_int]
+        rc = self.lib.lamehip_batch_set_incremental_replaygain(self.b, 1 if on else 0)
+        if rc != 0:
+            raise RuntimeError("lamehip_batch_set_incremental_replaygain failed (%d): %s" % (rc, last_error()))
+
     def radio_gain(self, s):
         """Stream s's radio gain in tenths of a dB, as lame_get_RadioGain reports it (0: no 50 ms window completed)."""
         self.lib.lamehip_batch_radio_gain.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]

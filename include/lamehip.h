@@ -263,7 +263,7 @@ int     lamehip_batch_set_device_resampling(lamehip_batch *, int on);
  * kernel launch (lamehip_batch_last_resample_ms: that launch) in front of the encode launch, lamehip_batch_finish also
  * the flush.  Capacity counts input samples; an append is also refused (-1, nothing counted) when its stream, flushed
  * right after the call, would exceed the float pool -- lamehip_batch_finish therefore never lacks room.  Device packing
- * and ReplayGain stay refused on an incremental batch.  Until the first append the batch takes whole streams as before.
+ * stays refused on an incremental batch, ReplayGain is refused unless lamehip_batch_set_incremental_replaygain.  Until the first append the batch takes whole streams as before.
  * An allocation failure returns LAMEHIP_ERR_DEVICE and leaves the batch as it was. */
 int     lamehip_batch_set_incremental_resampling(lamehip_batch *, int on);
 /* test accessor: the converted signal of a stream (float planes as the encoder reads them), valid after
@@ -318,19 +318,43 @@ float   lamehip_batch_last_ingest_ms(lamehip_batch *);
  * and the same samples handed over a frame's worth (1152, MPEG-2 / 2.5: 576 input samples) per lame_encode_buffer call
  * with lame_set_findReplayGain(1).  Call it before lamehip_batch_encode.  The proto's lame_set_findReplayGain is not
  * inherited.  -1 on an incremental batch, and once it is on lamehip_batch_append / _encode_available / _finish return -1
- * (lamehip_last_error); LAMEHIP_ERR_DEVICE when an allocation fails, the batch is then as it was.
+ * (lamehip_last_error) unless lamehip_batch_set_incremental_replaygain (below) opened them; LAMEHIP_ERR_DEVICE when an allocation fails, the batch is then as it was.
  * The window sums of a launch stay on the device until a getter or a tagged output asks for them; a lamehip_batch_encode
  * that finds those of the launch before it still there fetches them first, and for that WAITS for the batch's stream on the
  * host.  A caller that pipelines rounds reads the gains of a round (lamehip_batch_radio_gain, after lamehip_batch_sync or
  * the fetch) before it encodes the next. */
 int     lamehip_batch_set_replaygain(lamehip_batch *, int on);
+/* ReplayGain of an incremental batch, carried round by round on the device.  Accepted only before any PCM, length, mirror or
+ * append has been handed over (-1 after, lamehip_last_error() names this call); before or after
+ * lamehip_batch_set_sample_type; on a batch that converts the rate only with lamehip_batch_set_incremental_resampling on
+ * already (-1, the error names that call); never on a batch that packs on the device (-1).  on = 0 before the first append
+ * puts the batch back as it was; an allocation failure returns LAMEHIP_ERR_DEVICE and leaves the batch as it was.
+ * With it on, lamehip_batch_append, _append_input, _append_input_device and _append_device are accepted: each is one call of
+ * the reference entry point the batch's sample type is named after, made with lame_set_findReplayGain(1) -- the reference
+ * hands its analysis a call's samples in blocks of at most one frame counted from the call's start (a converting batch: the
+ * blocks the converter makes), and the analysis cuts its sums at a block's start, so the window sums depend on how the stream
+ * is cut into calls.  lamehip_batch_encode_available and lamehip_batch_finish run ONE launch of the gain kernel over what was
+ * appended since the last round (lamehip_batch_finish: the flush as well), behind the append and conversion launches, on the
+ * batch's stream and timed by events of its own (lamehip_batch_last_gain_ms: that launch; not part of
+ * lamehip_batch_last_kernel_ms).  Filter histories, the open window's sums and the samples heard stay in HBM between rounds;
+ * a round that brings a stream nothing leaves its state untouched.  lamehip_batch_get_gain_windows returns the windows
+ * finished so far after any round (they come home with the round's wait); lamehip_batch_radio_gain is valid after
+ * lamehip_batch_finish -- what lame_get_RadioGain returns on the handle API after lame_encode_flush for the same settings and
+ * the same sequence of calls -- and -1 before (the error names lamehip_batch_finish: the handle has no value before its flush
+ * either).  lamehip_batch_reset clears carried state, windows and gains.  An append whose stream, flushed right after the
+ * call, would be longer than the analysis takes (0x7fffff00 samples) is refused: -1, nothing counted, the error names the
+ * call.  Until the first append the batch behaves as one with lamehip_batch_set_replaygain(b, 1): whole streams through
+ * lamehip_batch_encode.  An incremental batch has no tagged output, so the gain is not written into a tag. */
+int     lamehip_batch_set_incremental_replaygain(lamehip_batch *, int on);
 /* stream's radio gain in tenths of a dB (0 when not one 50 ms window was completed); waits for the batch's stream.  -1
- * before a lamehip_batch_encode with the switch on, and again after lamehip_batch_reset. */
+ * before a lamehip_batch_encode with the switch on, and again after lamehip_batch_reset; on an incremental batch -1 before
+ * lamehip_batch_finish. */
 int     lamehip_batch_radio_gain(lamehip_batch *, int stream, int *tenths_db);
 /* test accessor: what the kernel measured, (left sum, right sum) of the squares of every completed window; writes the first
- * cap_windows pairs and returns the number of windows, or a negative code */
+ * cap_windows pairs and returns the number of windows, or a negative code (an incremental batch: the windows finished so far) */
 long    lamehip_batch_get_gain_windows(lamehip_batch *, int stream, double *lr_pairs, long cap_windows);
-/* HIP-event time in ms of the gain kernel of the last lamehip_batch_encode (after lamehip_batch_sync); 0 when none ran.  Like
+/* HIP-event time in ms of the gain kernel of the last lamehip_batch_encode (after lamehip_batch_sync), or of the last
+ * lamehip_batch_encode_available / _finish of a batch that measures round by round; 0 when none ran.  Like
  * lamehip_batch_last_resample_ms it is not part of lamehip_batch_last_kernel_ms / _parts_ms.  (The kernel has two mappings
  * of its serial part with the same results; the number of streams in a launch picks the faster, environment
  * LAMEHIP_GAIN_LANES=0 / 1 forces one: measurement, tests.) */
@@ -361,8 +385,8 @@ int     lamehip_batch_finish(lamehip_batch *);
  * another type.  -1, with a lamehip_last_error() that names the call: a stream that would exceed the capacity, a stride
  * other than 1 or 2, a finished batch, a batch that converts the sample rate without
  * lamehip_batch_set_incremental_resampling (with it the chunks are at the input rate and go to the input pool as they
- * are, see there), a batch that packs on the device or measures ReplayGain (the gain plan depends on how the reference is
- * called chunk by chunk: not built yet).
+ * are, see there), a batch that packs on the device or measures ReplayGain -- refused unless
+ * lamehip_batch_set_incremental_replaygain, which has the gain plan follow the calls chunk by chunk.
  * LAMEHIP_ERR_DEVICE when an allocation fails, the batch is then as it was.
  *   lamehip_batch_append_input         host buffers, l and r `stride' elements from sample to sample as for
  *                                      lamehip_batch_set_input; staged in the pinned arena like the shorts of
