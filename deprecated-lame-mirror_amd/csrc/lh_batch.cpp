@@ -28,6 +28,8 @@ extern "C" int lh_launch_gain(int floats, const LhGainParams * p, const LhGainSt
 extern "C" int lh_launch_gain_resume(int floats, const LhGainParams * p, const LhGainStream * streams, int nstreams, const int *tails,
                                      const void *pool, double *pairs, LhGainCarry * carry, void *stream);
 extern "C" void lh_pcm_copy_plane(void *dst, const void *src, int esz, int stride, long n);
+extern "C" int lh_launch_tag(const LhTagParams * p, const LhStreamDesc * descs, const LhStreamState * states, const LhFrameOut * out,
+                             unsigned char *bytes, const unsigned char *tmpl, const int *padding, int nstreams, void *stream);
 
 /* per device: the end of the last launch that filled it (lamehip_batch_encode) */
 static LhLaunchSerial &
@@ -93,6 +95,22 @@ struct lamehip_batch {
     LhDevBuf < uint8_t > d_bytes;
     std::vector < long long >bytes_off;
     std::vector < LhStreamDesc > h_desc;
+    /* device tagging on top of it (lamehip_batch_set_device_tagging): every stream's slice of the byte pool starts with room
+     * for the Xing/Info + LAME tag frame (bytes_off[] and LhStreamDesc.bytes_base point behind it: the encode kernel, its
+     * packer and the audio getters see what they always saw), lh_tag.hip fills the room behind the encode kernel from the
+     * template the switch made, and the fetch brings whole file images home.  The radio gain, which becomes a number on the
+     * host, is patched into an image when it is handed out. */
+    int     dev_tag = 0;
+    int     tagged = 0;         /* the last lamehip_batch_encode ran with the switch on ... */
+    int     tag_room = 0;       /* ... and left this much room in front of every stream's audio (0: the tag does not fit a frame) */
+    LhTagParams tag_p = {};
+    LhDevBuf < unsigned char >d_tag_tmpl;
+    LhDevBuf < int >d_tag_pad;
+    std::vector < int >h_tag_pad;       /* the end padding per stream, as the last launch's kernel read it */
+    std::vector < char >tag_patched;    /* stream s's image in h_bytes carries its gain */
+    LhEvent ev_tag[2];
+    int     tag_ran = 0;        /* the last lamehip_batch_encode launched the tag kernel (between ev_tag[0] and ev_tag[1]) */
+    float   tag_ms = 0;
     LhStream stream;
     LhEvent ev0, ev1;
     float   last_ms = 0;
@@ -2550,6 +2568,14 @@ batch_stream_bytes(const lamehip_batch * b, int s)
     return b->dev_pack ? (long long) b->nframes[(size_t) s] * max_frame_bytes : 0;
 }
 
+/* device tagging: the room in front of every stream's audio in the byte pool -- the tag frame's size, constant per batch; 0
+ * with the switch off, or when the tag does not fit a frame (lh_tag_init) */
+static int
+batch_tag_room(const lamehip_batch * b)
+{
+    return (b->dev_pack && b->dev_tag) ? b->tag_p.total : 0;
+}
+
 /* room for a launch of `total' frames whose streams' slices add up to `bytes_total' */
 static int
 batch_pools_reserve(lamehip_batch * b, long long total, long long bytes_total)
@@ -2575,6 +2601,7 @@ lamehip_batch_encode(lamehip_batch * b)
      * sample, so the carried state must be the initial one */
     if (b->encoded && batch_reset_states(b) != 0)
         return LAMEHIP_ERR_DEVICE;
+    int const room = batch_tag_room(b);
     for (int s = 0; s < b->B; s++) {
         LhStreamDesc & d = b->h_desc[(size_t) s];
         b->out_off[(size_t) s] = total;
@@ -2587,12 +2614,15 @@ lamehip_batch_encode(lamehip_batch * b)
         d.frame_end = b->nframes[(size_t) s];
         d.flush = 1;
         d.mid_rel = 0;
-        d.bytes_base = bytes_total;
+        d.bytes_base = bytes_total + room;      /* (device tagging: the tag frame's room comes first) */
         d.bytes_cap = batch_stream_bytes(b, s);
-        b->bytes_off[(size_t) s] = bytes_total;
-        bytes_total += d.bytes_cap;
+        b->bytes_off[(size_t) s] = d.bytes_base;
+        bytes_total += room + d.bytes_cap;
         total += b->nframes[(size_t) s];
     }
+    b->tagged = b->dev_pack && b->dev_tag;
+    b->tag_room = room;
+    b->tag_ran = 0;
     {
         int const rc = batch_pools_reserve(b, total, bytes_total);
         if (rc)
@@ -2610,6 +2640,14 @@ lamehip_batch_encode(lamehip_batch * b)
     }
     HIPCHK(hipMemcpyAsync(b->d_desc.get(), b->h_desc.data(), (size_t) b->B * sizeof(LhStreamDesc),
                           hipMemcpyHostToDevice, b->stream));
+    if (room > 0) {
+        /* device tagging: what the tag kernel cannot know -- every stream's end padding -- travels with the descriptors */
+        for (int s = 0; s < b->B; s++) {
+            b->h_tag_pad[(size_t) s] = batch_padding(b, s);
+            b->tag_patched[(size_t) s] = 0;
+        }
+        HIPCHK(hipMemcpyAsync(b->d_tag_pad.get(), b->h_tag_pad.data(), (size_t) b->B * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    }
     /* device conversion, or the ingest of a typed pool: behind the upload wait, in front of the analysis kernels */
     b->in_ran = 0;
     if (b->dev_rs) {
@@ -2664,6 +2702,17 @@ lamehip_batch_encode(lamehip_batch * b)
             rc = lh_launch_summary(b->d_state.get(), b->d_sum.get(), b->B, (void *) (hipStream_t) b->stream);
             if (rc)
                 return set_err("summary launch", (hipError_t) rc);
+            if (room > 0) {
+                /* device tagging: the tag frames, right behind -- in the serial order for the summary's reason, and in front
+                 * of ev_sum, which the fetch's copy of the bytes waits for */
+                HIPCHK(hipEventRecord(b->ev_tag[0], b->stream));
+                rc = lh_launch_tag(&b->tag_p, b->d_desc.get(), b->d_state.get(), b->d_out.get(), b->d_bytes.get(), b->d_tag_tmpl.get(),
+                                   b->d_tag_pad.get(), b->B, (void *) (hipStream_t) b->stream);
+                if (rc)
+                    return set_err("tag launch", (hipError_t) rc);
+                HIPCHK(hipEventRecord(b->ev_tag[1], b->stream));
+                b->tag_ran = 1;
+            }
             HIPCHK(hipEventRecord(b->ev_sum, b->stream));
         }
         if (big) {
@@ -2692,7 +2741,7 @@ lamehip_batch_fetch(lamehip_batch * b)
     if (b->fetched)
         return 0;
     for (int s = 0; s < b->B; s++)
-        total += b->h_desc[(size_t) s].bytes_cap;
+        total += b->tag_room + b->h_desc[(size_t) s].bytes_cap;
     HIPCHK(b->d_sum.reserve((size_t) b->B * 2));
     HIPCHK(b->h_sum.reserve((size_t) b->B * 2));
     HIPCHK(b->h_bytes.reserve((size_t) total));
@@ -2739,7 +2788,171 @@ lamehip_batch_set_device_packing(lamehip_batch * b, int on)
     if (!b)
         return -1;
     b->dev_pack = on != 0;
+    if (!b->dev_pack)
+        b->dev_tag = 0;         /* (the tag frames go in front of the device packer's bytes) */
     return 0;
+}
+
+/* Device tagging, on top of device packing: behind the encode kernel one more kernel (lh_tag.hip) writes every stream's
+ * final Xing/Info + LAME tag frame into HBM, directly in front of the stream's audio bytes, and lamehip_batch_fetch brings
+ * complete file images home (lamehip_batch_image_ptr / _get_images_all; lamehip_batch_get_bytes_tagged copies the same
+ * image instead of walking and summing the bytes on the host).  The audio getters return what they returned.  Before
+ * lamehip_batch_encode; may be switched between launches.  When the tag does not fit a frame (lh_tag_init) the images are
+ * the audio alone. */
+extern "C" int
+lamehip_batch_set_device_tagging(lamehip_batch * b, int on)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b)
+        return -1;
+    if (b->incremental) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_device_tagging: this batch is fed with lamehip_batch_append (incremental use), "
+                 "which takes the host packer; the tag frames go in front of the device packer's bytes (lamehip_batch_set_device_packing)");
+        return -1;
+    }
+    if (!b->dev_pack) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_device_tagging: for a batch that packs on the device "
+                 "(lamehip_batch_set_device_packing first)");
+        return -1;
+    }
+    if (!on || b->d_tag_pad.get()) {
+        b->dev_tag = on != 0;
+        return 0;
+    }
+    /* everything new first: a failure leaves the batch as it was */
+    LhVbrTag v;
+    LhTagParams p;
+    int const total = lh_tag_init(&v, &b->cfg);
+    if (b->rate_in)
+        v.samplerate_in = b->rate_in;
+    lh_tag_params(&v, &b->cfg, &p);
+    LhDevBuf < unsigned char >tmpl;
+    LhDevBuf < int >pad;
+    LhEvent ev[2];
+    std::vector < int >h_pad;
+    std::vector < char >patched;
+    std::vector < unsigned char >h_tmpl((size_t) (total > 0 ? total : 1), 0);
+    if (total > 0)
+        lh_tag_template(&v, &b->cfg, b->cfg.vbr_q, h_tmpl.data());
+    hipError_t e = tmpl.alloc(h_tmpl.size());
+    if (e == hipSuccess)
+        e = pad.alloc((size_t) b->B);
+    if (e == hipSuccess)
+        e = ev[0].create();
+    if (e == hipSuccess)
+        e = ev[1].create();
+    if (e == hipSuccess)
+        e = hipMemcpy(tmpl.get(), h_tmpl.data(), h_tmpl.size(), hipMemcpyHostToDevice);
+    try {
+        h_pad.assign((size_t) b->B, 0);
+        patched.assign((size_t) b->B, 0);
+    }
+    catch(const std::bad_alloc &) {
+        e = hipErrorOutOfMemory;
+    }
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        return set_err("lamehip_batch_set_device_tagging: device allocation", e);
+    }
+    b->d_tag_tmpl = std::move(tmpl);
+    b->d_tag_pad = std::move(pad);
+    b->ev_tag[0] = std::move(ev[0]);
+    b->ev_tag[1] = std::move(ev[1]);
+    b->h_tag_pad = std::move(h_pad);
+    b->tag_patched = std::move(patched);
+    b->tag_p = p;
+    b->dev_tag = 1;
+    return 0;
+}
+
+/* HIP-event time of the tag kernel of the last lamehip_batch_encode (after lamehip_batch_sync); 0 when none ran.  Not part
+ * of lamehip_batch_last_kernel_ms. */
+extern "C" float
+lamehip_batch_last_tag_ms(lamehip_batch * b)
+{
+    return b ? b->tag_ms : 0.0f;
+}
+
+/* Device tagging: the radio gain into stream s's image (tag frame first), which the kernel wrote with the field zero -- the
+ * window sums become a gain on the host (batch_gain_fetch) --: the two bytes of the field, and the frame's own CRC over
+ * them again (lh_tag.h).  *done (the image in the pinned buffer): once per stream and launch. */
+static int
+batch_image_gain(lamehip_batch * b, int s, unsigned char *image, char *done)
+{
+    LhVbrTag v;
+    if (b->tag_room <= 0 || b->nframes[(size_t) s] == 0 || (done && *done))
+        return 0;
+    memset(&v, 0, sizeof(v));
+    if (batch_tag_gain(b, s, &v) != 0)
+        return LAMEHIP_ERR_DEVICE;
+    if (v.radio_gain_on)
+        lh_tag_patch_gain(image, b->tag_p.at, v.radio_gain);
+    if (done)
+        *done = 1;
+    return 0;
+}
+
+/* who: one of the image getters of a batch whose last launch wrote the tag frames */
+static int
+batch_images_ready(lamehip_batch * b, const char *who)
+{
+    if (!b || !b->encoded || !b->dev_pack)
+        return -1;
+    if (!b->tagged) {
+        snprintf(g_err, sizeof(g_err), "%s: no lamehip_batch_encode with lamehip_batch_set_device_tagging on has run", who);
+        return -1;
+    }
+    return 0;
+}
+
+/* stream s's finished file image -- tag frame, then audio -- in the batch's pinned buffer (valid until the batch is encoded
+ * again): returns its length, or a negative code.  Waits for lamehip_batch_fetch, like lamehip_batch_bytes_ptr. */
+extern "C" long
+lamehip_batch_image_ptr(lamehip_batch * b, int s, const unsigned char **image)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    const unsigned char *audio = nullptr;
+    if (!b || s < 0 || s >= b->B || !image || batch_images_ready(b, "lamehip_batch_image_ptr") != 0)
+        return -1;
+    long const n = lamehip_batch_bytes_ptr(b, s, &audio);
+    if (n < 0)
+        return n;
+    unsigned char *const at = b->h_bytes.get() + b->bytes_off[(size_t) s] - b->tag_room;
+    if (batch_image_gain(b, s, at, b->tag_room > 0 ? &b->tag_patched[(size_t) s] : nullptr) != 0)
+        return LAMEHIP_ERR_DEVICE;
+    *image = at;
+    return n + b->tag_room;
+}
+
+/* all streams' file images: stream s at out + s * out_stride, sizes[s] = bytes or a negative code */
+extern "C" int
+lamehip_batch_get_images_all(lamehip_batch * b, unsigned char *out, long out_stride, long *sizes)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int     bad = 0;
+    if (!out || !sizes || batch_images_ready(b, "lamehip_batch_get_images_all") != 0)
+        return -1;
+    if (lamehip_batch_fetch(b) != 0)
+        return LAMEHIP_ERR_DEVICE;
+    HIPCHK(hipStreamSynchronize(b->down_stream));
+    for (int s = 0; s < b->B; s++) {
+        long    n = (b->nframes[(size_t) s] == 0) ? 0 : (long) b->h_sum.get()[2 * s];
+        unsigned char *const at = b->h_bytes.get() + b->bytes_off[(size_t) s] - b->tag_room;
+        if (b->h_sum.get()[2 * s + 1] != 0)
+            n = LAMEHIP_ERR_PAYLOAD;
+        else if (n + b->tag_room > out_stride)
+            n = -1;
+        else if (batch_image_gain(b, s, at, b->tag_room > 0 ? &b->tag_patched[(size_t) s] : nullptr) != 0)
+            n = LAMEHIP_ERR_DEVICE;
+        else
+            n += b->tag_room;
+        sizes[s] = n;
+        if (n < 0)
+            bad++;
+        else if (n > 0)
+            memcpy(out + (size_t) s * (size_t) out_stride, at, (size_t) n);
+    }
+    return bad ? -1 : 0;
 }
 
 /* Device rate conversion (a batch whose input rate differs from the encoder's): the input stays s16, in a pool at the
@@ -3012,6 +3225,19 @@ lamehip_batch_get_bytes_tagged(lamehip_batch * b, int s, unsigned char *out, lon
     long    k, pos = 0;
     if (!b || s < 0 || s >= b->B || !b->encoded || !b->dev_pack)
         return -1;
+    if (b->tagged && b->tag_room > 0) {
+        /* device tagging: the tag frame lies in front of the bytes in HBM; only the gain is the host's */
+        LhDeviceScope const on_device(b->device);
+        if (out_size < b->tag_room)
+            return -1;
+        k = lamehip_batch_get_bytes(b, s, out + b->tag_room, out_size - b->tag_room);
+        if (k < 0)
+            return k;
+        HIPCHK(hipMemcpy(out, b->d_bytes.get() + b->bytes_off[(size_t) s] - b->tag_room, (size_t) b->tag_room, hipMemcpyDeviceToHost));
+        if (batch_image_gain(b, s, out, nullptr) != 0)
+            return LAMEHIP_ERR_DEVICE;
+        return k + b->tag_room;
+    }
     total = lh_tag_init(&v, &b->cfg);
     if (b->rate_in)
         v.samplerate_in = b->rate_in;
@@ -3081,7 +3307,7 @@ lamehip_batch_reserve(lamehip_batch * b)
         return 0;               /* (incremental batches launch what has arrived: sized per launch) */
     for (int s = 0; s < b->B; s++) {
         total += b->nframes[(size_t) s];
-        bytes_total += batch_stream_bytes(b, s);
+        bytes_total += batch_tag_room(b) + batch_stream_bytes(b, s);
     }
     {
         int const rc = batch_pools_reserve(b, total, bytes_total);
@@ -3131,6 +3357,11 @@ lamehip_batch_sync(lamehip_batch * b)
         if (b->rg_ran && hipEventElapsedTime(&b->rg_ms, b->ev_rg[0], b->ev_rg[1]) != hipSuccess) {
             (void) hipGetLastError();
             b->rg_ms = 0;
+        }
+        b->tag_ms = 0;
+        if (b->tag_ran && hipEventElapsedTime(&b->tag_ms, b->ev_tag[0], b->ev_tag[1]) != hipSuccess) {
+            (void) hipGetLastError();
+            b->tag_ms = 0;
         }
         if (hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess)
             b->last_ms = ms;
@@ -3212,6 +3443,16 @@ lamehip_batch_get_frames(lamehip_batch * b, int s, void *frames_out, int max_fra
     return n;
 }
 
+
+/* test accessor: the device packer's byte pool in HBM as the last lamehip_batch_reserve / lamehip_batch_encode left it
+ * (device tagging: the tag frames' room included), and its size; NULL when there is none */
+extern "C" void *
+lamehip_batch_bytes_device_ptr(lamehip_batch * b, long long *size)
+{
+    if (size)
+        *size = b ? (long long) b->d_bytes.cap() : 0;
+    return b ? (void *) b->d_bytes.get() : nullptr;
+}
 
 /* debug / profiling aid: raw LhStreamState of one stream */
 extern "C" int

@@ -6,6 +6,7 @@
 
 #include "lamehip_types.h"
 #include "lh_rs_sample.h"
+#include "lh_tag.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -122,7 +123,7 @@ int     lh_bs_pending(const LhBitstream * bs);
 
 /* ---- Xing/Info + LAME tag bookkeeping (lh_vbrtag.c; reference VbrTag.c) ---- */
 #define LH_LAMEHEADERSIZE (4 + 4 + 4 + 4 + 100 + 4 + 9 + 1 + 1 + 8 + 1 + 1 + 3 + 1 + 1 + 2 + 4 + 2 + 2)
-#define LH_TAG_BAG 400
+#define LH_TAG_BAG LH_TAG_BAG_SIZE      /* 400 (lh_tag.h) */
 typedef struct LhVbrTag {
     int     enabled;
     int     total_frame_size;
@@ -143,6 +144,10 @@ void    lh_tag_crc(LhVbrTag * v, const unsigned char *buf, long n);
 int     lh_tag_placeholder(const LhVbrTag * v, const LhConfig * c, unsigned char *buf);
 int     lh_tag_frame(const LhVbrTag * v, const LhConfig * c, int vbr_q, int enc_padding, int last_mode_ext,
                      unsigned char *buf, long size);
+/* lh_tag_frame's first half -- the frame as far as the settings decide it, total_frame_size bytes -- and what the tag
+ * kernel of a device-packed batch (lh_tag.hip) needs besides it; the second half is lh_tag.h's, host and device */
+void    lh_tag_template(const LhVbrTag * v, const LhConfig * c, int vbr_q, unsigned char *buf);
+void    lh_tag_params(const LhVbrTag * v, const LhConfig * c, LhTagParams * p);
 int     lh_end_padding(long nsamples);
 int     lh_end_padding_fs(long nsamples, int samples_per_frame);
 

@@ -1,0 +1,319 @@
+/*
+ * lh_tag.hip -- the Xing/Info + LAME tag frames of a device-packed batch on the device (gfx950): behind the encode kernel,
+ * lh_tag_kernel writes every stream's final tag frame into the room in front of its audio bytes, byte for byte what
+ * lamehip_batch_get_bytes_tagged makes of the same bytes on the host (lh_vbrtag.c), so that the batch's fetch brings
+ * complete file images home.  A workgroup of LH_TAG_NT lanes takes one stream:
+ *   A  the music CRC-16 over the stream's audio bytes (reflected polynomial 0xA001, initial value 0: lh_tag_crc).  The
+ *      CRC is linear over GF(2) and leading zero bytes leave it at 0, so the bytes -- less the few behind the last
+ *      16-byte boundary of memory -- are thought of as padded in front to whole rows of LH_TAG_ROW bytes; in every row a
+ *      lane takes the LH_TAG_PIECE bytes at its place, one 16-byte load the wave's lanes make side by side, and brings
+ *      its own CRC from piece to piece over the rest of the row as if that were zeros (a 16 x 16 bit matrix, columns in
+ *      scalar registers: LhTagParams.adv).  The lanes' CRCs then fold pairwise, acc = advance(lower, bytes of the upper)
+ *      ^ upper, through six butterfly steps in a wave and across the waves in LDS, and lane 0 takes the bytes behind the
+ *      last boundary one by one.  A piece that reaches out of the stream is loaded byte by byte, inside it only: nothing
+ *      in front of the slice and nothing at or behind em_next_header is ever read.  The byte step (lh_tag_crc_byte) needs
+ *      no table: 64 lanes indexing a 256-entry table in LDS by byte would collide on its banks, and the polynomial's
+ *      three taps make a byte a dozen VALU instructions.
+ *   B  the bookkeeping of lh_tag_add_frame over the launch's LhFrameOut records, in closed form: after n frames the
+ *      sampling distance `want' is the smallest power of two with n / want < 400, the bag holds pos = n / want samples,
+ *      and sample j is the sum of the first (j + 1) want bit rates -- a prefix sum, 256 frames per step.
+ *   C  the frame: the host's template (lh_tag_template) into LDS, the seek table's 99 entries a lane each, the other
+ *      fields and the two CRCs over the frame in lane 0 (lh_tag.h, the text lh_tag_frame runs on the host), and out.
+ * A stream without frames gets zeros, as does one whose packer reported a status (which the getters report).
+ * Built with -ffp-contract=off like every object of the library; lh_tag.h names the seek table's roundings.
+ */
+#include <stdint.h>
+#include <math.h>
+
+#ifdef LH_EMU
+#include "hipemu.h"
+#define LH_TAG_FN static inline
+#else
+#include <hip/hip_runtime.h>
+#define LH_TAG_DEVICE
+#define LH_TAG_FN static __device__ __forceinline__
+#endif
+#include "lh_wave.h"
+#include "lh_device.h"
+#include "lh_tag.h"
+
+#define LH_TAG_WAVES (LH_TAG_NT / 64)
+#define LH_TAG_MAX_FRAME 2880   /* lh_tag_init allows no larger frame */
+
+struct LhTagLds {
+    unsigned char frame[LH_TAG_MAX_FRAME];
+    int     bag[LH_TAG_BAG_SIZE];
+    int     wave_sum[LH_TAG_WAVES];
+    uint32_t wave_crc[LH_TAG_WAVES];
+};
+
+struct LhTagPiece {
+    uint32_t w[4];
+};
+
+typedef uint32_t lh_tag_v4 __attribute__((vector_size(16)));
+
+/* the piece `off' bytes from `bytes' (at a multiple of 16 in memory) of the bytes [0, hi) there: what lies outside counts as
+ * zero and is not read */
+LH_TAG_FN LhTagPiece
+tag_piece(const unsigned char *bytes, long long off, long long hi)
+{
+    LhTagPiece v = { {0, 0, 0, 0} };
+    if (off >= 0 && off + LH_TAG_PIECE <= hi) {
+        lh_tag_v4 const t = *(const lh_tag_v4 *) __builtin_assume_aligned(bytes + off, LH_TAG_PIECE);
+        v.w[0] = t[0];
+        v.w[1] = t[1];
+        v.w[2] = t[2];
+        v.w[3] = t[3];
+    }
+    else if (off + LH_TAG_PIECE > 0 && off < hi) {
+        for (int j = 0; j < LH_TAG_PIECE; j++)
+            if (off + j >= 0 && off + j < hi)
+                v.w[j >> 2] |= (uint32_t) bytes[off + j] << (8 * (j & 3));
+    }
+    return v;
+}
+
+/* A: the music CRC of the n bytes at `bytes'; all lanes of the workgroup call it, lane 0 gets the result */
+LH_TAG_FN uint32_t
+tag_music_crc(const LhTagParams & p, const unsigned char *bytes, long long n, LhTagLds & lds)
+{
+    int const tid = (int) threadIdx.x, lane = lh_lane(), wave = lh_wave_id();
+    /* (places count from the stream's first byte, `lead' bytes behind a 16-byte boundary of memory; the body ends at the
+     * last such boundary in front of the stream's end) */
+    long long const lead = (long long) ((uintptr_t) bytes & (LH_TAG_PIECE - 1));
+    long long const body = ((lead + n) & ~(long long) (LH_TAG_PIECE - 1)) - lead;
+    long long const rows = body > 0 ? (body + lead + LH_TAG_ROW - 1) / LH_TAG_ROW : 0;
+    long long q = body - rows * LH_TAG_ROW + (long long) tid * LH_TAG_PIECE;
+    uint32_t acc = 0;
+    LhTagPiece cur = { {0, 0, 0, 0} };
+    if (rows > 0)
+        cur = tag_piece(bytes, q, body);
+    for (long long r = 0; r < rows; r++) {
+        /* (the next piece is on its way while this one is worked through) */
+        LhTagPiece next = { {0, 0, 0, 0} };
+        if (r + 1 < rows)
+            next = tag_piece(bytes, q + LH_TAG_ROW, body);
+        acc = lh_tag_crc_advance(acc, p.adv[LH_TAG_ADV_GAP]);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            acc = lh_tag_crc_byte(acc, cur.w[k]);
+            acc = lh_tag_crc_byte(acc, cur.w[k] >> 8);
+            acc = lh_tag_crc_byte(acc, cur.w[k] >> 16);
+            acc = lh_tag_crc_byte(acc, cur.w[k] >> 24);
+        }
+        cur = next;
+        q += LH_TAG_ROW;
+    }
+    /* the lanes of a wave, pairwise: the lower half's CRC moves on over the upper half's bytes */
+#pragma unroll
+    for (int j = 0; j < LH_TAG_ADV_WAVE; j++) {
+        int const d = 1 << j;
+        uint32_t const other = lh_shfl_u32(acc, lane ^ d);
+        uint32_t const lower = (lane & d) ? other : acc, upper = (lane & d) ? acc : other;
+        acc = lh_tag_crc_advance(lower, p.adv[j]) ^ upper;
+    }
+    if (lane == 0)
+        lds.wave_crc[wave] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        acc = lds.wave_crc[0];
+        for (int k = 1; k < LH_TAG_WAVES; k++)
+            acc = lh_tag_crc_advance(acc, p.adv[LH_TAG_ADV_WAVE]) ^ lds.wave_crc[k];
+        for (long long a = body > 0 ? body : 0; a < n; a++)
+            acc = lh_tag_crc_byte(acc, bytes[a]);
+    }
+    return acc;
+}
+
+/* B: what n calls of lh_tag_add_frame leave -- the bag in LDS, its fill, the sampling distance and the sum -- from the
+ * bit-rate indices of the records fr[0 .. n); all lanes of the workgroup call it and get the three figures */
+LH_TAG_FN void
+tag_bag(const LhTagParams & p, const LhFrameOut * fr, int n, LhTagLds & lds, int *pos, int *want, int *sum)
+{
+    int const tid = (int) threadIdx.x, lane = lh_lane(), wave = lh_wave_id();
+    int     w = 1, running = 0;
+    while (n / w >= LH_TAG_BAG_SIZE)
+        w += w;
+    for (int t0 = 0; t0 < n; t0 += LH_TAG_NT) {
+        int const f = t0 + tid;
+        uint32_t v = f < n ? (uint32_t) p.kbps[fr[f].bitrate_index & 15] : 0u;
+        int     base = running, tile = 0;
+        for (int d = 1; d < 64; d += d) {
+            uint32_t const below = lh_shfl_u32(v, lane - d);
+            if (lane >= d)
+                v += below;
+        }
+        if (lane == 63)
+            lds.wave_sum[wave] = (int) v;
+        __syncthreads();
+        for (int k = 0; k < LH_TAG_WAVES; k++) {
+            if (k < wave)
+                base += lds.wave_sum[k];
+            tile += lds.wave_sum[k];
+        }
+        if (f < n && (f + 1) % w == 0 && (f + 1) / w - 1 < LH_TAG_BAG_SIZE)
+            lds.bag[(f + 1) / w - 1] = base + (int) v;
+        running += tile;
+        __syncthreads();
+    }
+    *pos = n / w;
+    *want = w;
+    *sum = running;
+}
+
+/* one stream: its tag frame to `tag' (p.total bytes), from the n audio bytes at `audio' and its nf frames' records */
+LH_TAG_FN void
+tag_stream(const LhTagParams & p, const unsigned char *audio, long long n, const LhFrameOut * fr, int nf, int enc_padding,
+           const unsigned char *tmpl, unsigned char *tag, LhTagLds & lds)
+{
+    int const tid = (int) threadIdx.x;
+    int     pos, want, sum;
+    if (nf <= 0) {
+        for (int i = tid; i < p.total; i += LH_TAG_NT)
+            tag[i] = 0;
+        return;
+    }
+    uint32_t const crc = tag_music_crc(p, audio, n, lds);
+    tag_bag(p, fr, nf, lds, &pos, &want, &sum);
+    for (int i = tid; i < p.total; i += LH_TAG_NT)
+        lds.frame[i] = tmpl[i];
+    __syncthreads();
+    if (tid >= 1 && tid < 100)
+        lds.frame[p.at + LH_TAG_AT_TOC + tid] = lh_tag_toc_entry(tid, lds.bag, pos, sum);
+    __syncthreads();
+    if (tid == 0)
+        lh_tag_finish_fields(lds.frame, p.at, p.sideinfo_len, p.error_protection, (uint32_t) nf, (uint32_t) (n + p.total), crc,
+                             enc_padding, fr[nf - 1].mode_ext);
+    __syncthreads();
+    for (int i = tid; i < p.total; i += LH_TAG_NT)
+        tag[i] = lds.frame[i];
+}
+
+/* grid: one workgroup per stream.  descs / states: the launch's; out: its records; bytes: the pool, in which stream s's
+ * audio starts at descs[s].bytes_base with p.total bytes of room for the tag in front; padding: the end padding per stream */
+__global__ void
+__launch_bounds__(LH_TAG_NT)
+lh_tag_kernel(LhTagParams p, const LhStreamDesc * descs, const LhStreamState * states, const LhFrameOut * out, unsigned char *bytes,
+              const unsigned char *tmpl, const int *padding, int nstreams)
+{
+    __shared__ LhTagLds lds;
+    int const s = (int) blockIdx.x;
+    if (s >= nstreams)
+        return;
+    long long const base = descs[s].bytes_base, cap = descs[s].bytes_cap, n = states[s].em_next_header;
+    int     nf = descs[s].frame_end - descs[s].frame_begin;
+    /* (no tag for a stream whose packer gave up, or whose length is not one its slice could hold) */
+    if (states[s].status != 0 || n < 0 || n > cap)
+        nf = 0;
+    tag_stream(p, bytes + base, n, out + descs[s].out_index, nf, padding[s], tmpl, bytes + base - p.total, lds);
+}
+
+#ifndef LH_EMU
+/* Returns a hipError_t. */
+extern "C" int
+lh_launch_tag(const LhTagParams * p, const LhStreamDesc * descs, const LhStreamState * states, const LhFrameOut * out, unsigned char *bytes,
+              const unsigned char *tmpl, const int *padding, int nstreams, void *stream)
+{
+    if (nstreams <= 0)
+        return 0;
+    if (p->total < 1 || p->total > LH_TAG_MAX_FRAME || p->at < 4 || p->at + LH_TAG_AT_EXT + LH_TAG_EXT_CRC + 2 > p->total)
+        return (int) hipErrorInvalidValue;
+    hipLaunchKernelGGL(lh_tag_kernel, dim3((unsigned) nstreams), dim3(LH_TAG_NT), 0, (hipStream_t) stream, *p, descs, states, out, bytes,
+                       tmpl, padding, nstreams);
+    return (int) hipGetLastError();
+}
+#else
+/* TEST ENTRY POINTS (tests/hipemu_tag): the kernel's parts and the kernel under the fiber emulator */
+extern "C" int
+lh_emu_tag_crc(const LhTagParams * params, const unsigned char *bytes, long long n, unsigned *crc)
+{
+    LhTagParams const p = *params;
+    hipemu_dim3 grid = { 1, 1, 1 }, block = { LH_TAG_NT, 1, 1 };
+    hipemu_run(grid, block,[=] () {
+               __shared__ LhTagLds lds;
+               uint32_t const c = tag_music_crc(p, bytes, n, lds);
+               if (threadIdx.x == 0)
+                   *crc = c;
+               }
+    );
+    return 0;
+}
+
+/* bag: LH_TAG_BAG_SIZE entries, of which pos are written; psw: pos, want, sum */
+extern "C" int
+lh_emu_tag_bag(const LhTagParams * params, const signed char *bitrate_index, int n, int *bag, int *psw)
+{
+    LhTagParams const p = *params;
+    std::vector < LhFrameOut > fr((size_t) (n > 0 ? n : 1));
+    hipemu_dim3 grid = { 1, 1, 1 }, block = { LH_TAG_NT, 1, 1 };
+    for (int f = 0; f < n; f++)
+        fr[(size_t) f].bitrate_index = bitrate_index[f];
+    const LhFrameOut *const frames = fr.data();
+    hipemu_run(grid, block,[=] () {
+               __shared__ LhTagLds lds;
+               int     pos, want, sum;
+               tag_bag(p, frames, n, lds, &pos, &want, &sum);
+               if (threadIdx.x == 0) {
+                   psw[0] = pos;
+                   psw[1] = want;
+                   psw[2] = sum;
+                   for (int j = 0; j < pos; j++)
+                       bag[j] = lds.bag[j];
+               }
+               }
+    );
+    return 0;
+}
+
+/* the host's gain patch of lh_tag.h, as this library compiled it */
+extern "C" void
+lh_emu_tag_patch_gain(unsigned char *frame, int at, int radio_gain)
+{
+    lh_tag_patch_gain(frame, at, radio_gain);
+}
+
+/* the kernel over nstreams streams.  Per stream: audio bytes, status and frame count as the encode kernel would leave
+ * them, the end padding, the last frame's mode extension; bitrate_index: the streams' lists one behind the other;
+ * bytes_base: where each stream's audio starts in `pool' (the tag goes in front) */
+extern "C" int
+lh_emu_tag(const LhTagParams * params, const unsigned char *tmpl, int nstreams, const long long *nbytes, const int *status,
+           const int *nframes, const int *padding, const int *last_mode_ext, const signed char *bitrate_index,
+           const long long *bytes_base, const long long *bytes_cap, unsigned char *pool)
+{
+    LhTagParams const p = *params;
+    std::vector < LhStreamDesc > descs((size_t) nstreams);
+    std::vector < LhStreamState > states((size_t) nstreams);
+    long long total = 0;
+    for (int s = 0; s < nstreams; s++)
+        total += nframes[s];
+    std::vector < LhFrameOut > fr((size_t) (total > 0 ? total : 1));
+    total = 0;
+    for (int s = 0; s < nstreams; s++) {
+        memset(&descs[(size_t) s], 0, sizeof(LhStreamDesc));
+        memset(&states[(size_t) s], 0, sizeof(LhStreamState));
+        descs[(size_t) s].out_index = total;
+        descs[(size_t) s].frame_end = nframes[s];
+        descs[(size_t) s].bytes_base = bytes_base[s];
+        descs[(size_t) s].bytes_cap = bytes_cap[s];
+        states[(size_t) s].status = status[s];
+        states[(size_t) s].em_next_header = nbytes[s];
+        for (int f = 0; f < nframes[s]; f++) {
+            fr[(size_t) (total + f)].bitrate_index = bitrate_index[total + f];
+            fr[(size_t) (total + f)].mode_ext = (int8_t) (f == nframes[s] - 1 ? last_mode_ext[s] : 3 - last_mode_ext[s]);
+        }
+        total += nframes[s];
+    }
+    const LhStreamDesc *const d = descs.data();
+    const LhStreamState *const st = states.data();
+    const LhFrameOut *const frames = fr.data();
+    hipemu_dim3 grid = { (unsigned) nstreams, 1, 1 }, block = { LH_TAG_NT, 1, 1 };
+    if (nstreams <= 0)
+        return 0;
+    hipemu_run(grid, block,[=] () {
+               lh_tag_kernel(p, d, st, frames, pool, tmpl, padding, nstreams);
+               }
+    );
+    return 0;
+}
+#endif

@@ -16,6 +16,8 @@
 #include <string.h>
 #include "lh_host.h"
 
+typedef char lh_tag_delay_is_the_encoders[LH_TAG_ENCDELAY == LH_ENCDELAY ? 1 : -1];
+
 static uint16_t lh_crc16_tab[256];
 static int lh_crc16_ready = 0;
 
@@ -166,59 +168,22 @@ put_i2(unsigned char *b, int x)
     b[1] = (unsigned char) (x & 0xff);
 }
 
-/* final tag frame; returns the frame size, 0 when there is no tag (reference VbrTag.c:900-1018).
- * user_quality / vbr_q are the caller-level settings the "quality" byte is made of. */
-int
-lh_tag_frame(const LhVbrTag * v, const LhConfig * c, int vbr_q, int enc_padding, int last_mode_ext,
-             unsigned char *buf, long size)
+/* The frame as far as the settings decide it (lh_tag.h): the header with mode extension 0, "Info" / "Xing", the flags, the
+ * static fields of the LAME extension -- v's source rate, radio gain and nogap place among them --, everything a stream
+ * decides left zero.  Writes v->total_frame_size bytes. */
+void
+lh_tag_template(const LhVbrTag * v, const LhConfig * c, int vbr_q, unsigned char *buf)
 {
-    unsigned char toc[100];
-    int     i, n;
-    uint16_t crc = 0;
-    if (!v->enabled || v->pos <= 0)
-        return 0;
-    if (size < v->total_frame_size)
-        return v->total_frame_size;
-    if (!buf)
-        return 0;
+    int     n;
     memset(buf, 0, (size_t) v->total_frame_size);
-    tag_frame_header(c, last_mode_ext, buf);
-    memset(toc, 0, sizeof(toc));
-    for (i = 1; i < 100; ++i) {
-        /* entry i = where i percent of the playing time lies, in 1/256 of the byte count: the
-         * bag sample nearest below, relative to the final sum (float index and ratio, double
-         * scaling, as the reference's Xing_seek_table evaluates them) */
-        float const percent = i / (float) 100;
-        int     slot = (int) (floor(percent * v->pos)), where;
-        float   upto, all;
-        slot = slot > v->pos - 1 ? v->pos - 1 : slot;
-        upto = (float) v->bag[slot];
-        all = (float) v->sum;
-        where = (int) (256. * upto / all);
-        toc[i] = (unsigned char) (where > 255 ? 255 : where);
-    }
+    tag_frame_header(c, 0, buf);
     n = c->sideinfo_len;
     if (c->error_protection)
         n -= 2;
     memcpy(buf + n, c->vbr == 0 ? "Info" : "Xing", 4);   /* reference VbrTag.c:964-977 */
     n += 4;
     put_i4(buf + n, 0x0001 | 0x0002 | 0x0004 | 0x0008);    /* frames, bytes, TOC, quality */
-    n += 4;
-    put_i4(buf + n, (uint32_t) v->num_frames);
-    n += 4;
-    put_i4(buf + n, (uint32_t) (v->bytes_written + (unsigned long) v->total_frame_size));
-    n += 4;
-    memcpy(buf + n, toc, sizeof(toc));
-    n += (int) sizeof(toc);
-    if (c->error_protection) {
-        /* the tag frame carries a header CRC like any other frame (reference VbrTag.c:996-999); it
-         * covers the first bytes of the tag, which start two bytes early in this case */
-        unsigned const hc = lh_header_crc(buf, c->sideinfo_len);
-        buf[4] = (unsigned char) (hc >> 8);
-        buf[5] = (unsigned char) (hc & 255u);
-    }
-    for (i = 0; i < n; i++)
-        crc = crc16_update(buf[i], crc);
+    n += 4 + 4 + 4 + 100;       /* (the counts and the seek table: the stream's) */
     {
         /* LAME extension, reference PutLameVBR */
         unsigned char *p = buf + n;
@@ -229,7 +194,6 @@ lh_tag_frame(const LhVbrTag * v, const LhConfig * c, int vbr_q, int enc_padding,
         int const ath_type = c->ATHtype;
         int const safe_joint = (c->use_safe_joint_stereo != 0);
         int     stereo_mode, source_freq, non_optimal = 0;
-        unsigned long const music_length = v->bytes_written + (unsigned long) v->total_frame_size;
         if (quality < 0)
             quality = 0;
         switch (c->mode) {
@@ -270,17 +234,7 @@ lh_tag_frame(const LhVbrTag * v, const LhConfig * c, int vbr_q, int enc_padding,
         p[k++] = lowpass;
         put_i4(p + k, 0);               /* peak signal amplitude: not measured */
         k += 4;
-        {
-            /* radio ReplayGain (reference VbrTag.c:704-721): name code 1, originator "automatic", sign, |gain| in
-             * tenths of a dB; all zero when it was not measured */
-            unsigned field = 0;
-            if (v->radio_gain_on) {
-                int     rg = v->radio_gain;
-                rg = rg > 0x1FE ? 0x1FE : (rg < -0x1FE ? -0x1FE : rg);
-                field = 0x2000u | 0xC00u | (rg >= 0 ? (unsigned) rg : (0x200u | (unsigned) -rg));
-            }
-            put_i2(p + k, (uint16_t) field);
-        }
+        put_i2(p + k, (uint16_t) lh_tag_gain_field(v->radio_gain_on, v->radio_gain));   /* radio ReplayGain */
         k += 2;
         put_i2(p + k, 0);               /* audiophile ReplayGain */
         k += 2;
@@ -296,23 +250,57 @@ lh_tag_frame(const LhVbrTag * v, const LhConfig * c, int vbr_q, int enc_padding,
                 : lh_bitrate_row(c->version)[c->vbr_min_bitrate_index];
             p[k++] = (unsigned char) (abr >= 255 ? 0xFF : abr);
         }
-        p[k] = (unsigned char) (LH_ENCDELAY >> 4);
-        p[k + 1] = (unsigned char) ((LH_ENCDELAY << 4) + (enc_padding >> 8));
-        p[k + 2] = (unsigned char) enc_padding;
-        k += 3;
+        k += 3;                         /* (encoder delay and end padding: with the stream's fields) */
         p[k++] = (unsigned char) (c->noise_shaping + (stereo_mode << 2) + (non_optimal << 5) + (source_freq << 6));
         p[k++] = 0;                     /* MP3 gain */
         /* preset: apply_preset(brate) leaves the bit rate here (presets.c:361, lame.c:1045);
          * the VBR path applies V0..V9 = 500 - 10 q (lame.c:983) */
         put_i2(p + k, (c->vbr == 0 || c->vbr == 3) ? c->avg_bitrate : 500 - 10 * c->vbr_q);
-        k += 2;
-        put_i4(p + k, (uint32_t) music_length);
-        k += 4;
-        put_i2(p + k, v->music_crc);
-        k += 2;
-        for (i = 0; i < k; i++)
-            crc = crc16_update(p[i], crc);
-        put_i2(p + k, crc);
     }
+}
+
+/* what the tag kernel of a device-packed batch needs besides the template (lh_tag.h) */
+void
+lh_tag_params(const LhVbrTag * v, const LhConfig * c, LhTagParams * p)
+{
+    static const long run[LH_TAG_NADV] = { 16, 32, 64, 128, 256, 512, 64 * LH_TAG_PIECE, LH_TAG_ROW - LH_TAG_PIECE };
+    int     j, k;
+    long    i;
+    memset(p, 0, sizeof(*p));
+    p->total = v->total_frame_size;
+    p->at = c->sideinfo_len - (c->error_protection ? 2 : 0);
+    p->sideinfo_len = c->sideinfo_len;
+    p->error_protection = c->error_protection != 0;
+    for (k = 0; k < 16; k++)
+        p->kbps[k] = lh_bitrate_row(c->version)[k];
+    for (j = 0; j < LH_TAG_NADV; j++)
+        for (k = 0; k < 16; k++) {
+            uint32_t crc = 1u << k;
+            for (i = 0; i < run[j]; i++)
+                crc = lh_tag_crc_byte(crc, 0);
+            p->adv[j][k] = (uint16_t) crc;
+        }
+}
+
+/* final tag frame; returns the frame size, 0 when there is no tag (reference VbrTag.c:900-1018): the template, finished
+ * with the stream's own fields (lh_tag.h).  vbr_q is the caller-level setting the "quality" byte is made of. */
+int
+lh_tag_frame(const LhVbrTag * v, const LhConfig * c, int vbr_q, int enc_padding, int last_mode_ext,
+             unsigned char *buf, long size)
+{
+    int const at = c->sideinfo_len - (c->error_protection ? 2 : 0);
+    uint32_t const music_length = (uint32_t) (v->bytes_written + (unsigned long) v->total_frame_size);
+    int     i;
+    if (!v->enabled || v->pos <= 0)
+        return 0;
+    if (size < v->total_frame_size)
+        return v->total_frame_size;
+    if (!buf)
+        return 0;
+    lh_tag_template(v, c, vbr_q, buf);
+    for (i = 1; i < 100; ++i)
+        buf[at + LH_TAG_AT_TOC + i] = lh_tag_toc_entry(i, v->bag, v->pos, v->sum);
+    lh_tag_finish_fields(buf, at, c->sideinfo_len, c->error_protection, (uint32_t) v->num_frames, music_length, v->music_crc,
+                         enc_padding, last_mode_ext);
     return v->total_frame_size;
 }

@@ -426,6 +426,53 @@ class Batch:
         self.lib.lamehip_batch_set_device_packing.argtypes = [C.c_void_p, C.c_int]
         assert self.lib.lamehip_batch_set_device_packing(self.b, 1 if on else 0) == 0
 
+    def set_device_tagging(self, on=True):
+        """A device-packed batch (set_device_packing() first): one more kernel behind the encode kernel writes every
+        stream's final tag frame in front of its bytes in HBM, and fetch() brings complete file images home -- image(),
+        images_all(); get_bytes_tagged() then copies the same image.  Before encode(); may be switched between launches."""
+        self.lib.lamehip_batch_set_device_tagging.argtypes = [C.c_void_p, C.c_int]
+        rc = self.lib.lamehip_batch_set_device_tagging(self.b, 1 if on else 0)
+        if rc:
+            raise RuntimeError("lamehip_batch_set_device_tagging failed (%d): %s" % (rc, last_error()))
+
+    def image(self, s):
+        """Stream s's finished file image -- tag frame, then audio -- in the batch's pinned buffer (waits for fetch()); a
+        uint8 view, no copy, valid until the next encode()."""
+        self.lib.lamehip_batch_image_ptr.restype = C.c_long
+        self.lib.lamehip_batch_image_ptr.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        p = C.c_void_p()
+        k = self.lib.lamehip_batch_image_ptr(self.b, s, C.byref(p))
+        if k < 0:
+            raise RuntimeError("lamehip_batch_image_ptr failed (%d): %s" % (k, last_error()))
+        if k == 0:
+            return np.zeros(0, dtype=np.uint8)
+        return np.frombuffer((C.c_uint8 * k).from_address(p.value), dtype=np.uint8)
+
+    def images_all(self, stride=None):
+        """(buffer [B, stride] uint8, sizes) of the streams' file images."""
+        if stride is None:
+            stride = (max(self.frames(s) for s in range(self.n)) + 2) * 1500 + 2880
+        out = np.empty((self.n, stride), dtype=np.uint8)
+        sizes = np.zeros(self.n, dtype=np.int64)
+        self.lib.lamehip_batch_get_images_all.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]
+        rc = self.lib.lamehip_batch_get_images_all(self.b, out.ctypes.data, stride, sizes.ctypes.data)
+        if rc:
+            raise RuntimeError("lamehip_batch_get_images_all failed (%d): %s" % (rc, last_error()))
+        return out, sizes
+
+    def bytes_device_ptr(self):
+        """(device address, size) of the device packer's byte pool as the last reserve() / encode() left it (test accessor)."""
+        self.lib.lamehip_batch_bytes_device_ptr.restype = C.c_void_p
+        self.lib.lamehip_batch_bytes_device_ptr.argtypes = [C.c_void_p, C.c_void_p]
+        n = C.c_longlong(0)
+        return self.lib.lamehip_batch_bytes_device_ptr(self.b, C.byref(n)), int(n.value)
+
+    def tag_ms(self):
+        """HIP-event time of the last encode()'s tag kernel, 0 when none ran."""
+        self.lib.lamehip_batch_last_tag_ms.restype = C.c_float
+        self.lib.lamehip_batch_last_tag_ms.argtypes = [C.c_void_p]
+        return float(self.lib.lamehip_batch_last_tag_ms(self.b))
+
     def set_device_resampling(self, on=True):
         """A batch whose input rate differs from the encoder's: convert on the device (inside encode()) instead of
         on the host (inside set_pcm()); opens set_pcm_device / pcm_device_ptr / set_length / pcm_host for it.

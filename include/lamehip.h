@@ -449,6 +449,31 @@ int     lamehip_batch_fetch(lamehip_batch *);
 long    lamehip_batch_bytes_ptr(lamehip_batch *, int stream, const unsigned char **bytes);
 /* tag frame + audio frames, like lamehip_batch_pack_tagged, from the device-packed bytes */
 long    lamehip_batch_get_bytes_tagged(lamehip_batch *, int stream, unsigned char *out, long out_size);
+/* Tagging on the device, on top of device packing: with this switched on (before lamehip_batch_encode; it may be switched
+ * between launches) one more kernel behind the encode kernel writes every stream's final Xing/Info + LAME tag frame into
+ * HBM, directly in front of the stream's audio bytes -- the music CRC over the bytes, the seek table, the counts, the frame's
+ * own CRCs (reference VbrTag.c: lame_get_lametag_frame; csrc/lh_tag.hip) --, and lamehip_batch_fetch brings complete file
+ * images home, contiguous and ready to be written to disk:
+ *   lamehip_batch_image_ptr      like lamehip_batch_bytes_ptr: waits for the fetch; the stream's image -- tag frame, then
+ *                                audio -- in place in the pinned buffer (valid until the next encode), returns its length,
+ *                                LAMEHIP_ERR_PAYLOAD when the device packer reported a status, or another negative code;
+ *   lamehip_batch_get_images_all like lamehip_batch_get_bytes_all: image s at out + s * out_stride, sizes[s] = bytes or a
+ *                                negative code;
+ *   lamehip_batch_get_bytes_tagged  returns the same image, copied from HBM instead of made on the host.
+ * The images are those of lamehip_batch_pack_tagged, byte for byte (a radio gain measured by lamehip_batch_set_replaygain is
+ * put into the image when it is handed out); when the tag does not fit a frame they are the audio alone, as there.
+ * lamehip_batch_get_bytes / _get_bytes_all / _bytes_ptr return the audio alone, as before.  Returns -1 unless the batch packs
+ * on the device (lamehip_batch_set_device_packing first) and on an incremental batch; a failed allocation returns
+ * LAMEHIP_ERR_DEVICE and leaves the batch as it was.  Off (the default): launches, layouts and bytes are what they were. */
+int     lamehip_batch_set_device_tagging(lamehip_batch *, int on);
+long    lamehip_batch_image_ptr(lamehip_batch *, int stream, const unsigned char **image);
+int     lamehip_batch_get_images_all(lamehip_batch *, unsigned char *out, long out_stride, long *sizes);
+/* HIP-event time of the tag kernel of the last lamehip_batch_encode in ms (after lamehip_batch_sync; events of its own: not
+ * part of lamehip_batch_last_kernel_ms or of its parts); 0 when the kernel did not run */
+float   lamehip_batch_last_tag_ms(lamehip_batch *);
+/* test accessor: the device packer's byte pool in HBM as the last lamehip_batch_reserve / lamehip_batch_encode left it (with
+ * device tagging the tag frames' room is part of it) and its size in bytes; NULL when there is none */
+void   *lamehip_batch_bytes_device_ptr(lamehip_batch *, long long *size);
 /* raw payload access for tests: copies frames [0, n) of a stream (LhFrameOut[]) */
 int     lamehip_batch_get_frames(lamehip_batch *, int stream, void *frames_out, int max_frames);
 /* debug aid: raw per-stream carried state (LhStreamState, csrc/lh_device.h) */
