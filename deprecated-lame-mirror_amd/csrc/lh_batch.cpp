@@ -12,6 +12,7 @@
 #include "lh_pcm_in.h"
 #include "lh_gain.h"
 #include "lh_replaygain_tables.h"
+#include "lh_drain.h"
 
 extern "C" int lh_launch_resample_typed(int type, const LhRsParams * p, const float *bank, const LhRsBlock * trunk, const LhRsBlock * tails,
                                         const LhRsStream * streams, int nstreams, int max_blocks, const void *pcm, float *pcmf,
@@ -30,6 +31,9 @@ extern "C" int lh_launch_gain_resume(int floats, const LhGainParams * p, const L
 extern "C" void lh_pcm_copy_plane(void *dst, const void *src, int esz, int stride, long n);
 extern "C" int lh_launch_tag(const LhTagParams * p, const LhStreamDesc * descs, const LhStreamState * states, const LhFrameOut * out,
                              unsigned char *bytes, const unsigned char *tmpl, const int *padding, int nstreams, void *stream);
+extern "C" int lh_launch_drain(const LhDrainParams * p, const LhStreamDesc * descs, const LhStreamState * states, const long long *drained,
+                               long long *carry, const unsigned char *pool, LhDrainRow * rows, int nstreams, const LhDrainTile * tiles,
+                               long long ntiles, unsigned char *round, long long round_cap, void *stream);
 
 /* per device: the end of the last launch that filled it (lamehip_batch_encode) */
 static LhLaunchSerial &
@@ -207,6 +211,32 @@ struct lamehip_batch {
     long    stage_used = 0;     /* shorts staged */
     int     stage_nseg = 0;     /* chunks staged by lamehip_batch_append */
     int     finished = 0;       /* lamehip_batch_finish has run: the streams are closed */
+    /* ... on the device packer (lamehip_batch_set_incremental_packing on top of lamehip_batch_set_device_packing): every stream
+     * has a fixed slice of the byte pool d_bytes, laid out at the first append from the batch's capacity -- the encode kernel
+     * writes at absolute positions across the rounds --, no LhFrameOut comes home and no host packer runs; behind a round's
+     * encode launch lh_drain.hip finds what every stream has finished and gathers it from `drained' on into d_round, and the
+     * round's table and bytes come home to h_dr_rows / h_round, out of which lamehip_batch_drain / _drain_ptr hand them */
+    int     inc_pack = 0;
+    long long dr_slice = 0;     /* bytes of a stream's slice */
+    int     dr_frame_max = 0;   /* the largest frame the settings allow */
+    int     dr_have = 0;        /* h_dr_rows / h_round hold a round's drain */
+    std::vector < long long >dr_drained;        /* per stream: bytes handed out so far */
+    std::vector < long long >dr_sent;   /* ... as the round's launch sees them */
+    std::vector < long long >dr_bound;  /* per stream: the most the round can find */
+    std::vector < long long >dr_next;   /* per stream: where its frames ended when the last table came home */
+    std::vector < int >dr_done;         /* ... and how many there were */
+    std::vector < LhDrainTile > h_dr_tiles;
+    long long dr_padded = 0;    /* bytes of a round buffer that holds every stream's bound */
+    LhDevBuf < long long >d_dr_drained, d_dr_carry;
+    LhDevBuf < LhDrainTile > d_dr_tiles;
+    LhDevBuf < LhDrainRow > d_dr_rows;
+    LhPinned < LhDrainRow > h_dr_rows;  /* [B + 1]; a stream's n goes to 0 when it is handed out */
+    LhDevBuf < unsigned char >d_round;
+    LhPinned < unsigned char >h_round;
+    LhEvent ev_dr[2];
+    int     dr_ran = 0;         /* the last round launched the drain kernels (between ev_dr[0] and ev_dr[1]) */
+    float   dr_ms = 0;
+    std::vector < std::vector < unsigned char > >handed;        /* host packer: what lamehip_batch_drain_ptr last handed out */
     /* typed and device-resident appends (lamehip_batch_append_input / _append_input_device / _append_device): the table of
      * segments lh_append_kernel works through, pinned and in HBM -- entries [0, LH_STAGE_SEGS) for the chunks staged in the
      * arena, the B behind them for a round that comes from device buffers --, and the events around its launches */
@@ -1015,7 +1045,7 @@ batch_incremental_check(const lamehip_batch * b, const char *who, int typed_ok)
     }
     /* (how the reference converts the rate depends on how it is called, chunk by chunk: the conversion plan of a batch is
      * made for whole streams, unless lamehip_batch_set_incremental_resampling asked for the plan that follows the calls) */
-    if ((b->rate_in && !b->inc_rs) || b->dev_pack) {
+    if ((b->rate_in && !b->inc_rs) || (b->dev_pack && !b->inc_pack)) {
         snprintf(g_err, sizeof(g_err), "%s: incremental batches take the encoder's own input rate and the host packer, this batch %s", who,
                  !b->rate_in || b->inc_rs ? "packs on the device (lamehip_batch_set_device_packing)"
                  : b->dev_rs ? "converts the sample rate (lamehip_batch_set_incremental_resampling lets it do so round by round)"
@@ -1050,6 +1080,31 @@ batch_gain_restart(lamehip_batch * b)
     return 0;
 }
 
+static int batch_frame_max(const lamehip_batch * b);
+
+/* An incremental batch that packs on the device starts (over): the byte pool laid out -- once: every stream's slice holds
+ * the frames of a stream as long as the batch's capacity (the converted capacity when the batch converts), each as large as
+ * the settings allow, and never moves --, nothing handed out, every stream's header walk (lh_drain.hip) at its first byte. */
+static int
+batch_drain_begin(lamehip_batch * b)
+{
+    int const frame_max = batch_frame_max(b);
+    long long const slice = (long long) lh_total_frames_fs(b->inc_rs ? b->capf : b->cap, fs_of(b->cfg)) * frame_max;
+    HIPCHK(b->d_bytes.reserve((size_t) b->B * (size_t) slice));
+    HIPCHK(hipMemsetAsync(b->d_dr_carry.get(), 0, (size_t) b->B * sizeof(long long), b->stream));
+    b->dr_slice = slice;
+    b->dr_frame_max = frame_max;
+    b->dr_drained.assign((size_t) b->B, 0);
+    b->dr_next.assign((size_t) b->B, 0);
+    b->dr_done.assign((size_t) b->B, 0);
+    for (int s = 0; s < b->B; s++)
+        b->bytes_off[(size_t) s] = (long long) s * slice;
+    b->dr_have = 0;
+    b->dr_ran = 0;
+    b->dr_ms = 0;
+    return 0;
+}
+
 static int
 batch_incremental_begin(lamehip_batch * b, const char *who, int typed_ok)
 {
@@ -1057,8 +1112,11 @@ batch_incremental_begin(lamehip_batch * b, const char *who, int typed_ok)
         return 0;
     if (batch_incremental_check(b, who, typed_ok) != 0)
         return -1;
+    if (b->inc_pack && batch_drain_begin(b) != 0)
+        return LAMEHIP_ERR_DEVICE;
     if (batch_reset_states(b) != 0 || batch_gain_restart(b) != 0)
         return LAMEHIP_ERR_DEVICE;
+    b->handed.assign((size_t) b->B, std::vector < unsigned char >());
     b->fed.assign((size_t) b->B, 0);
     b->done.assign((size_t) b->B, 0);
     b->staged.assign((size_t) b->B, 0);
@@ -1691,6 +1749,128 @@ batch_tiles_done(lamehip_batch * b)
 static int batch_gain_round(lamehip_batch * b);
 static void batch_gain_round_done(lamehip_batch * b, int end);
 
+/* behind the round's wait: the time of its encode launch (lamehip_batch_last_kernel_ms) */
+static void
+batch_round_time(lamehip_batch * b)
+{
+    float   ms = 0;
+    if (hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess)
+        b->last_ms = ms;
+    else
+        (void) hipGetLastError();
+}
+
+/* A round on the device packer, in front of its launches: what the drain needs -- every stream's bound (the frames done
+ * after the round, each as large as the settings allow, less what has been handed out), the gather's tiles, room for the
+ * table, the tiles and the round buffer in HBM and in pinned memory.  Allocates; a failure returns LAMEHIP_ERR_DEVICE with
+ * nothing launched. */
+static int
+batch_drain_plan(lamehip_batch * b, const std::vector < int >&upto)
+{
+    b->dr_have = 0;             /* (the buffers may move; what has not been handed out is gathered again) */
+    try {
+        b->dr_bound.resize((size_t) b->B);
+        for (int s = 0; s < b->B; s++) {
+            int const frames = upto[(size_t) s] > b->done[(size_t) s] ? upto[(size_t) s] : b->done[(size_t) s];
+            b->dr_bound[(size_t) s] = lh_drain_bound(b->dr_next[(size_t) s], frames - b->dr_done[(size_t) s], b->dr_frame_max, b->dr_slice,
+                                                     b->dr_drained[(size_t) s]);
+        }
+        long long const ntiles = lh_drain_tiles(b->dr_bound.data(), b->B, nullptr, 0, &b->dr_padded);
+        b->h_dr_tiles.resize((size_t) ntiles);
+        (void) lh_drain_tiles(b->dr_bound.data(), b->B, b->h_dr_tiles.data(), ntiles, nullptr);
+        b->dr_sent = b->dr_drained;
+    }
+    catch(const std::bad_alloc &) {
+        snprintf(g_err, sizeof(g_err), "incremental packing: out of memory (drain plan)");
+        return LAMEHIP_ERR_DEVICE;
+    }
+    /* (twice what is needed; drained first: nothing of an earlier round is in flight, a round ends with a wait.  The pinned
+     * buffer may move: what lamehip_batch_drain_ptr handed out is valid until the next round) */
+    size_t const room = (size_t) b->dr_padded + 64;
+    HIPCHK(b->d_dr_tiles.reserve(b->h_dr_tiles.size() + 1, b->h_dr_tiles.size() + 1024, b->stream));
+    HIPCHK(b->d_round.reserve(room, room, b->stream));
+    HIPCHK(b->h_round.reserve(room, room, b->stream));
+    return 0;
+}
+
+/* ... and behind its encode launch: the table of tiles and `drained' to HBM, the three drain launches between ev_dr[0] and
+ * ev_dr[1], and the table on its way home */
+static int
+batch_drain_launch(lamehip_batch * b, int end)
+{
+    LhDrainParams p;
+    memset(&p, 0, sizeof(p));
+    p.sideinfo_len = b->cfg.sideinfo_len;
+    p.frame_factor = (b->cfg.version + 1) * 72000;
+    p.samplerate = b->cfg.samplerate;
+    p.final = end;
+    for (int i = 0; i < 16; i++)
+        p.kbps[i] = (int16_t) ((i > 0 && i < 15) ? lh_tag_kbps(b->cfg.version, i) : 0);
+    b->dr_have = 0;
+    if (!b->h_dr_tiles.empty())
+        HIPCHK(hipMemcpyAsync(b->d_dr_tiles.get(), b->h_dr_tiles.data(), b->h_dr_tiles.size() * sizeof(LhDrainTile), hipMemcpyHostToDevice,
+                              b->stream));
+    HIPCHK(hipMemcpyAsync(b->d_dr_drained.get(), b->dr_sent.data(), (size_t) b->B * sizeof(long long), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipEventRecord(b->ev_dr[0], b->stream));
+    int const rc = lh_launch_drain(&p, (const LhStreamDesc *) b->d_stage.get(), b->d_state.get(), b->d_dr_drained.get(), b->d_dr_carry.get(),
+                                   b->d_bytes.get(), b->d_dr_rows.get(), b->B, b->d_dr_tiles.get(), (long long) b->h_dr_tiles.size(),
+                                   b->d_round.get(), (long long) b->d_round.cap(), (void *) (hipStream_t) b->stream);
+    if (rc)
+        return set_err("drain launch", (hipError_t) rc);
+    HIPCHK(hipEventRecord(b->ev_dr[1], b->stream));
+    b->dr_ran = 1;
+    HIPCHK(hipMemcpyAsync(b->h_dr_rows.get(), b->d_dr_rows.get(), ((size_t) b->B + 1) * sizeof(LhDrainRow), hipMemcpyDeviceToHost, b->stream));
+    return 0;
+}
+
+/* ... and the way home: behind the table (the caller has waited for it) ONE copy of exactly the round's bytes, then the
+ * round's wait.  A stream whose packer reported a status -- or whose position the drain could not place in its slice --
+ * fails the round with LAMEHIP_ERR_PAYLOAD; the other streams' bytes are there. */
+static int
+batch_drain_home(lamehip_batch * b)
+{
+    const LhDrainRow *rows = b->h_dr_rows.get();
+    long long const total = rows[b->B].off;
+    b->dr_ms = 0;
+    if (b->dr_ran && hipEventElapsedTime(&b->dr_ms, b->ev_dr[0], b->ev_dr[1]) != hipSuccess) {
+        (void) hipGetLastError();
+        b->dr_ms = 0;
+    }
+    if (total < 0 || total > b->dr_padded) {
+        snprintf(g_err, sizeof(g_err), "incremental packing: the drain found %lld bytes where the round's bound is %lld", total, b->dr_padded);
+        return LAMEHIP_ERR_PAYLOAD;
+    }
+    for (int s = 0; s < b->B; s++)
+        if (rows[s].n < 0 || rows[s].n > b->dr_bound[(size_t) s] || rows[s].off < 0 || rows[s].off + rows[s].n > total) {
+            snprintf(g_err, sizeof(g_err), "incremental packing: the drain found %lld bytes of stream %d where its bound is %lld", rows[s].n, s,
+                     b->dr_bound[(size_t) s]);
+            return LAMEHIP_ERR_PAYLOAD;
+        }
+    if (total > 0) {
+        HIPCHK(hipMemcpyAsync(b->h_round.get(), b->d_round.get(), (size_t) total, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+    }
+    b->dr_have = 1;
+    return 0;
+}
+
+/* ... and the books: where every stream's frames end now (the next round's bounds start there), and the streams' statuses */
+static int
+batch_drain_done(lamehip_batch * b, const std::vector < int >&upto)
+{
+    const LhDrainRow *rows = b->h_dr_rows.get();
+    for (int s = 0; s < b->B; s++) {
+        b->dr_next[(size_t) s] = rows[s].next;
+        b->dr_done[(size_t) s] = upto[(size_t) s] > b->done[(size_t) s] ? upto[(size_t) s] : b->done[(size_t) s];
+    }
+    for (int s = 0; s < b->B; s++)
+        if (rows[s].status != 0) {
+            snprintf(g_err, sizeof(g_err), "device bit packer reported status %d for stream %d", rows[s].status, s);
+            return LAMEHIP_ERR_PAYLOAD;
+        }
+    return 0;
+}
+
 /* encode frames [done, upto[s]) of every stream and pack them into pending[]; `end' marks the
  * streams' last frames (flush) */
 static int
@@ -1713,9 +1893,16 @@ batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
         d.frame_begin = b->done[(size_t) s];
         d.frame_end = upto[(size_t) s];
         d.flush = end;
+        if (b->inc_pack) {
+            /* (the device packer: the stream's slice, the same in every round) */
+            d.bytes_base = b->bytes_off[(size_t) s];
+            d.bytes_cap = b->dr_slice;
+        }
         total += nf > 0 ? nf : 0;
     }
     HIPCHK(b->d_out.reserve((size_t) total, 1024));
+    if (b->inc_pack && total > 0 && (rc = batch_drain_plan(b, upto)) != 0)
+        return rc;
     /* descriptors, then what is staged (chunk table + the arena's bytes in use), then the scatter */
     HIPCHK(hipMemcpyAsync(b->d_stage.get(), b->h_stage.get(), (size_t) b->B * sizeof(LhStreamDesc), hipMemcpyHostToDevice, b->stream));
     if ((rc = batch_stage_flush(b, 0)) != 0)
@@ -1727,6 +1914,7 @@ batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
     if (b->inc_rg && (rc = batch_gain_round(b)) != 0)
         return rc;
     if (total == 0) {
+        b->dr_ms = 0;           /* (no drain either: what the last round brought home stays where it is) */
         HIPCHK(hipStreamSynchronize(b->stream));
         batch_append_time(b);
         batch_tiles_done(b);
@@ -1739,13 +1927,31 @@ batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
         if ((rc = batch_plan(b, descs, &plan)) != 0
             || (rc = batch_launch(b, batch_reads_floats(b) ? (const int16_t *) 0 : b->d_pcm.get(),
                                   batch_reads_floats(b) ? b->d_pcmf.get() : (const float *) 0, (const LhStreamDesc *) b->d_stage.get(), plan,
-                                  (uint8_t *) 0)) != 0)
+                                  b->inc_pack ? b->d_bytes.get() : (uint8_t *) 0)) != 0)
             return rc;
     }
     b->launched = 1;
+    if (b->inc_pack) {
+        /* the device packer: no record comes home and no host packer runs -- the drain kernels behind the encode launch, their
+         * table, the round's bytes in one copy (the emit stage has read its records in d_out on the device) */
+        if ((rc = batch_drain_launch(b, end)) != 0)
+            return rc;
+        HIPCHK(hipStreamSynchronize(b->stream));
+        batch_round_time(b);
+        batch_append_time(b);
+        batch_tiles_done(b);
+        batch_gain_round_done(b, end);
+        if ((rc = batch_drain_home(b)) == 0)
+            rc = batch_drain_done(b, upto);
+        for (int s = 0; s < b->B; s++)
+            if (upto[(size_t) s] > b->done[(size_t) s])
+                b->done[(size_t) s] = upto[(size_t) s];
+        return rc ? rc : (int) total;
+    }
     b->h_new.resize((size_t) total);
     HIPCHK(hipMemcpyAsync(b->h_new.data(), b->d_out.get(), (size_t) total * sizeof(LhFrameOut), hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
+    batch_round_time(b);
     batch_append_time(b);
     batch_tiles_done(b);
     batch_gain_round_done(b, end);
@@ -1913,10 +2119,19 @@ lamehip_batch_finish(lamehip_batch * b)
         b->nframes[(size_t) s] = lh_total_frames_fs(len, fs_of(b->cfg));
         upto[(size_t) s] = b->nframes[(size_t) s];
     }
+    if (b->inc_pack)
+        for (int s = 0; s < b->B; s++)
+            if (upto[(size_t) s] <= b->done[(size_t) s]) {
+                /* (the kernel's flush -- the stuffing that completes the last frame -- goes with a stream's last frame:
+                 * lh_total_frames_fs leaves every stream at least one for this round, whatever was fed) */
+                snprintf(g_err, sizeof(g_err), "lamehip_batch_finish: stream %d has no frame left for the flush (%d encoded, %d in all)", s,
+                         b->done[(size_t) s], upto[(size_t) s]);
+                return -1;
+            }
     n = batch_encode_range(b, upto, 1);
     if (n < 0)
         return n;
-    for (int s = 0; s < b->B; s++) {
+    for (int s = 0; s < b->B && !b->inc_pack; s++) {
         LhBitstream *bs = &b->packer[(size_t) s];
         std::vector < unsigned char >&out = b->pending[(size_t) s];
         size_t  at = out.size();
@@ -1937,6 +2152,19 @@ lamehip_batch_drain(lamehip_batch * b, int s, unsigned char *out, int cap)
     int     n;
     if (!b || !b->incremental || s < 0 || s >= b->B)
         return -1;
+    if (b->inc_pack) {
+        /* the device packer: out of the round's pinned buffer */
+        LhDrainRow & row = b->h_dr_rows.get()[s];
+        if (!b->dr_have || row.n <= 0)
+            return 0;
+        if (!out || (long long) cap < row.n)
+            return -1;
+        n = (int) row.n;
+        memcpy(out, b->h_round.get() + row.off, (size_t) n);
+        b->dr_drained[(size_t) s] += n;
+        row.n = 0;
+        return n;
+    }
     n = (int) b->pending[(size_t) s].size();
     if (n == 0)
         return 0;
@@ -1945,6 +2173,39 @@ lamehip_batch_drain(lamehip_batch * b, int s, unsigned char *out, int cap)
     memcpy(out, b->pending[(size_t) s].data(), (size_t) n);
     b->pending[(size_t) s].clear();
     return n;
+}
+
+/* the same bytes in place: in the round's pinned buffer on the device packer, in a buffer of the batch's on the host
+ * packer; valid until the next lamehip_batch_encode_available, _finish, _reset (host packer: or _drain_ptr of the stream).
+ * Counts as a drain. */
+extern "C" long
+lamehip_batch_drain_ptr(lamehip_batch * b, int s, const unsigned char **bytes)
+{
+    if (!b || !b->incremental || s < 0 || s >= b->B || !bytes)
+        return -1;
+    *bytes = nullptr;
+    if (b->inc_pack) {
+        LhDrainRow & row = b->h_dr_rows.get()[s];
+        if (!b->dr_have || row.n <= 0)
+            return 0;
+        long const n = (long) row.n;
+        *bytes = b->h_round.get() + row.off;
+        b->dr_drained[(size_t) s] += n;
+        row.n = 0;
+        return n;
+    }
+    b->handed[(size_t) s].clear();
+    b->handed[(size_t) s].swap(b->pending[(size_t) s]);
+    *bytes = b->handed[(size_t) s].empty() ? nullptr : b->handed[(size_t) s].data();
+    return (long) b->handed[(size_t) s].size();
+}
+
+/* HIP-event time of the drain kernels (lh_drain.hip) of the last lamehip_batch_encode_available / _finish of a batch that
+ * packs round by round on the device; 0 when none ran.  Not part of lamehip_batch_last_kernel_ms. */
+extern "C" float
+lamehip_batch_last_drain_ms(lamehip_batch * b)
+{
+    return b ? b->dr_ms : 0.0f;
 }
 
 extern "C" int
@@ -1968,6 +2229,7 @@ lamehip_batch_reset(lamehip_batch * b)
             if (lh_bs_init_sized(&b->packer[(size_t) s], 65536) != 0)
                 return -2;
             b->pending[(size_t) s].clear();
+            b->handed[(size_t) s].clear();
         }
         b->fed.assign((size_t) b->B, 0);
         b->done.assign((size_t) b->B, 0);
@@ -1978,6 +2240,9 @@ lamehip_batch_reset(lamehip_batch * b)
         b->ap_nseg = 0;
         b->ap_max_n = 0;
         b->finished = 0;
+        /* (a batch that packs on the device: nothing handed out, the header walks at the slices' first bytes) */
+        if (b->inc_pack && batch_drain_begin(b) != 0)
+            return LAMEHIP_ERR_DEVICE;
         /* (a batch that converts round by round: every stream's converter back in front of its first sample) */
         for (LhRsCursor & c:b->rs_cur)
             lh_rs_cursor_init(&c);
@@ -2442,9 +2707,10 @@ lamehip_batch_set_incremental_replaygain(lamehip_batch * b, int on)
         }
         return 0;
     }
-    if (b->dev_pack) {
+    if (b->dev_pack && !b->inc_pack) {
         snprintf(g_err, sizeof(g_err), "lamehip_batch_set_incremental_replaygain: not for a batch that packs on the device "
-                 "(lamehip_batch_set_device_packing), which incremental use does not");
+                 "(lamehip_batch_set_device_packing), which incremental use does not unless lamehip_batch_set_incremental_packing "
+                 "was called first");
         return -1;
     }
     if (b->rate_in && !b->inc_rs) {
@@ -2559,13 +2825,18 @@ lamehip_batch_last_gain_ms(lamehip_batch * b)
 
 /* The byte pool's slice of stream s (device packing; else 0): room for every frame at the largest frame size the settings
  * allow, +1 for CBR padding.  lamehip_batch_encode lays the streams out with it, lamehip_batch_reserve sizes the pool by it. */
-static long long
-batch_stream_bytes(const lamehip_batch * b, int s)
+static int
+batch_frame_max(const lamehip_batch * b)
 {
     int const top = (b->cfg.vbr == 0) ? b->cfg.bitrate_index : b->cfg.vbr_max_bitrate_index;
     /* (the row of the stream's MPEG version: an MPEG-2 / 2.5 index stands for half the MPEG-1 rate or less) */
-    int const max_frame_bytes = (b->cfg.version + 1) * 72000 * lh_tag_kbps(b->cfg.version, top & 15) / b->cfg.samplerate + 1;
-    return b->dev_pack ? (long long) b->nframes[(size_t) s] * max_frame_bytes : 0;
+    return (b->cfg.version + 1) * 72000 * lh_tag_kbps(b->cfg.version, top & 15) / b->cfg.samplerate + 1;
+}
+
+static long long
+batch_stream_bytes(const lamehip_batch * b, int s)
+{
+    return b->dev_pack ? (long long) b->nframes[(size_t) s] * batch_frame_max(b) : 0;
 }
 
 /* device tagging: the room in front of every stream's audio in the byte pool -- the tag frame's size, constant per batch; 0
@@ -2787,9 +3058,91 @@ lamehip_batch_set_device_packing(lamehip_batch * b, int on)
 {
     if (!b)
         return -1;
+    if (b->inc_pack && b->incremental) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_device_packing: this batch is fed with lamehip_batch_append and packs its rounds "
+                 "on the device (lamehip_batch_set_incremental_packing)");
+        return -1;
+    }
     b->dev_pack = on != 0;
-    if (!b->dev_pack)
+    if (!b->dev_pack) {
         b->dev_tag = 0;         /* (the tag frames go in front of the device packer's bytes) */
+        b->inc_pack = 0;        /* (and the rounds of an incremental batch are the device packer's) */
+    }
+    return 0;
+}
+
+/* Incremental use of a batch that packs on the device (lamehip_batch_set_device_packing first): the appends are accepted,
+ * every lamehip_batch_encode_available / _finish runs the encode kernel with its bit packer on every stream's fixed slice of
+ * the byte pool and, behind it, the drain kernels (lh_drain.hip), and lamehip_batch_drain / _drain_ptr hand out finished MP3
+ * bytes that came home in one copy -- no LhFrameOut record crosses to the host and no host packer runs.  Only before any PCM
+ * is handed over; not with device tagging (an incremental batch has no tagged output); lamehip_batch_set_incremental_resampling
+ * and _replaygain go on top when called after it.  on = 0 puts the batch back as it was. */
+extern "C" int
+lamehip_batch_set_incremental_packing(lamehip_batch * b, int on)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b)
+        return -1;
+    if (!b->dev_pack) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_incremental_packing: for a batch that packs on the device "
+                 "(lamehip_batch_set_device_packing first)");
+        return -1;
+    }
+    if (b->pcm_given || b->encoded || b->incremental) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_incremental_packing: only before any PCM is handed over");
+        return -1;
+    }
+    if (b->dev_tag) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_incremental_packing: not with lamehip_batch_set_device_tagging "
+                 "(an incremental batch has no tagged output)");
+        return -1;
+    }
+    if (!on || b->inc_pack) {
+        if (!on && b->inc_pack && (b->inc_rs || b->inc_rg)) {
+            snprintf(g_err, sizeof(g_err), "lamehip_batch_set_incremental_packing: lamehip_batch_set_incremental_resampling / _replaygain "
+                     "were switched on on top of it; switch them off first");
+            return -1;
+        }
+        b->inc_pack = on != 0 && b->inc_pack;
+        return 0;
+    }
+    /* everything new first: a failure leaves the batch as it was */
+    LhDevBuf < long long >drained, carry;
+    LhDevBuf < LhDrainRow > rows;
+    LhPinned < LhDrainRow > h_rows;
+    LhEvent ev[2];
+    std::vector < long long >h_drained;
+    hipError_t e = drained.alloc((size_t) b->B);
+    if (e == hipSuccess)
+        e = carry.alloc((size_t) b->B);
+    if (e == hipSuccess)
+        e = rows.alloc((size_t) b->B + 1);
+    if (e == hipSuccess)
+        e = h_rows.alloc((size_t) b->B + 1);
+    if (e == hipSuccess)
+        e = ev[0].create();
+    if (e == hipSuccess)
+        e = ev[1].create();
+    try {
+        h_drained.assign((size_t) b->B, 0);
+    }
+    catch(const std::bad_alloc &) {
+        e = hipErrorOutOfMemory;
+    }
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        return set_err("lamehip_batch_set_incremental_packing: allocation", e);
+    }
+    memset(h_rows.get(), 0, ((size_t) b->B + 1) * sizeof(LhDrainRow));
+    b->d_dr_drained = std::move(drained);
+    b->d_dr_carry = std::move(carry);
+    b->d_dr_rows = std::move(rows);
+    b->h_dr_rows = std::move(h_rows);
+    b->ev_dr[0] = std::move(ev[0]);
+    b->ev_dr[1] = std::move(ev[1]);
+    b->dr_drained = std::move(h_drained);
+    b->dr_have = 0;
+    b->inc_pack = 1;
     return 0;
 }
 
@@ -2813,6 +3166,11 @@ lamehip_batch_set_device_tagging(lamehip_batch * b, int on)
     if (!b->dev_pack) {
         snprintf(g_err, sizeof(g_err), "lamehip_batch_set_device_tagging: for a batch that packs on the device "
                  "(lamehip_batch_set_device_packing first)");
+        return -1;
+    }
+    if (on && b->inc_pack) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_device_tagging: this batch packs its rounds on the device "
+                 "(lamehip_batch_set_incremental_packing), and an incremental batch has no tagged output");
         return -1;
     }
     if (!on || b->d_tag_pad.get()) {

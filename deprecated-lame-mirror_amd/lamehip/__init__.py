@@ -415,6 +415,36 @@ class Batch:
             raise RuntimeError("lamehip_batch_drain: buffer of %d bytes too small" % cap)
         return buf.raw[:k]
 
+    def set_incremental_packing(self, on=True):
+        """Incremental use on the device bit packer (set_device_packing() first, before any PCM): the appends are accepted,
+        every encode_available() / finish() packs on the device and gathers what the streams finished into one pinned round
+        buffer (csrc/lh_drain.hip); drain() copies out of it, drain_view() hands the bytes out in place."""
+        self.lib.lamehip_batch_set_incremental_packing.argtypes = [C.c_void_p, C.c_int]
+        rc = self.lib.lamehip_batch_set_incremental_packing(self.b, 1 if on else 0)
+        if rc != 0:
+            raise RuntimeError("lamehip_batch_set_incremental_packing failed (%d): %s" % (rc, last_error()))
+
+    def drain_view(self, s):
+        """The bytes drain(s) would return, in place (a read-only numpy view of the batch's buffer, valid until the next
+        encode_available() / finish() / reset()); counts as a drain."""
+        self.lib.lamehip_batch_drain_ptr.restype = C.c_long
+        self.lib.lamehip_batch_drain_ptr.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(C.c_ubyte))]
+        p = C.POINTER(C.c_ubyte)()
+        k = self.lib.lamehip_batch_drain_ptr(self.b, s, C.byref(p))
+        if k < 0:
+            raise RuntimeError("lamehip_batch_drain_ptr failed (%d): %s" % (k, last_error()))
+        if k == 0:
+            return np.zeros(0, dtype=np.uint8)
+        v = np.ctypeslib.as_array(p, shape=(k,))
+        v.flags.writeable = False
+        return v
+
+    def drain_ms(self):
+        """HIP-event time of the drain kernels of the last encode_available() / finish() (set_incremental_packing())."""
+        self.lib.lamehip_batch_last_drain_ms.restype = C.c_float
+        self.lib.lamehip_batch_last_drain_ms.argtypes = [C.c_void_p]
+        return float(self.lib.lamehip_batch_last_drain_ms(self.b))
+
     def set_length(self, s, n):
         assert self.lib.lamehip_batch_set_length(self.b, s, n) == 0
 

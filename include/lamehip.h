@@ -263,7 +263,8 @@ int     lamehip_batch_set_device_resampling(lamehip_batch *, int on);
  * kernel launch (lamehip_batch_last_resample_ms: that launch) in front of the encode launch, lamehip_batch_finish also
  * the flush.  Capacity counts input samples; an append is also refused (-1, nothing counted) when its stream, flushed
  * right after the call, would exceed the float pool -- lamehip_batch_finish therefore never lacks room.  Device packing
- * stays refused on an incremental batch, ReplayGain is refused unless lamehip_batch_set_incremental_replaygain.  Until the first append the batch takes whole streams as before.
+ * stays refused on an incremental batch unless lamehip_batch_set_incremental_packing, ReplayGain is refused unless
+ * lamehip_batch_set_incremental_replaygain.  Until the first append the batch takes whole streams as before.
  * An allocation failure returns LAMEHIP_ERR_DEVICE and leaves the batch as it was. */
 int     lamehip_batch_set_incremental_resampling(lamehip_batch *, int on);
 /* test accessor: the converted signal of a stream (float planes as the encoder reads them), valid after
@@ -327,7 +328,8 @@ int     lamehip_batch_set_replaygain(lamehip_batch *, int on);
 /* ReplayGain of an incremental batch, carried round by round on the device.  Accepted only before any PCM, length, mirror or
  * append has been handed over (-1 after, lamehip_last_error() names this call); before or after
  * lamehip_batch_set_sample_type; on a batch that converts the rate only with lamehip_batch_set_incremental_resampling on
- * already (-1, the error names that call); never on a batch that packs on the device (-1).  on = 0 before the first append
+ * already (-1, the error names that call); on a batch that packs on the device only with
+ * lamehip_batch_set_incremental_packing on already (-1 otherwise).  on = 0 before the first append
  * puts the batch back as it was; an allocation failure returns LAMEHIP_ERR_DEVICE and leaves the batch as it was.
  * With it on, lamehip_batch_append, _append_input, _append_input_device and _append_device are accepted: each is one call of
  * the reference entry point the batch's sample type is named after, made with lame_set_findReplayGain(1) -- the reference
@@ -385,8 +387,9 @@ int     lamehip_batch_finish(lamehip_batch *);
  * another type.  -1, with a lamehip_last_error() that names the call: a stream that would exceed the capacity, a stride
  * other than 1 or 2, a finished batch, a batch that converts the sample rate without
  * lamehip_batch_set_incremental_resampling (with it the chunks are at the input rate and go to the input pool as they
- * are, see there), a batch that packs on the device or measures ReplayGain -- refused unless
- * lamehip_batch_set_incremental_replaygain, which has the gain plan follow the calls chunk by chunk.
+ * are, see there), a batch that packs on the device -- refused unless lamehip_batch_set_incremental_packing -- or measures
+ * ReplayGain -- refused unless lamehip_batch_set_incremental_replaygain, which has the gain plan follow the calls chunk by
+ * chunk.
  * LAMEHIP_ERR_DEVICE when an allocation fails, the batch is then as it was.
  *   lamehip_batch_append_input         host buffers, l and r `stride' elements from sample to sample as for
  *                                      lamehip_batch_set_input; staged in the pinned arena like the shorts of
@@ -410,6 +413,38 @@ int     lamehip_batch_append_device(lamehip_batch *, const void *dev, long long 
 /* HIP-event time in ms of the append launches since, and including, the last lamehip_batch_encode_available / _finish; not
  * part of lamehip_batch_last_kernel_ms / _parts_ms, like lamehip_batch_last_ingest_ms */
 float   lamehip_batch_last_append_ms(lamehip_batch *);
+/* Incremental use on the device bit packer.  Accepted only with lamehip_batch_set_device_packing on (-1 otherwise,
+ * lamehip_last_error() names that call), only before any PCM, length, mirror or append has been handed over, and not with
+ * lamehip_batch_set_device_tagging on (an incremental batch has no tagged output; device tagging is refused behind it
+ * likewise).  on = 0 before the first append puts the batch back as it was: a device-packed batch that refuses every
+ * append.  An allocation failure returns LAMEHIP_ERR_DEVICE and leaves the batch as it was.  With it on,
+ * lamehip_batch_append, _append_input, _append_input_device and _append_device are accepted, and
+ * lamehip_batch_set_incremental_resampling / _set_incremental_replaygain may be switched on behind it (both run in front of
+ * the encode launch, whichever packer follows).
+ * Every stream gets a fixed slice of the byte pool in HBM, laid out at the first append for a stream as long as the batch's
+ * capacity (the converted capacity when the batch converts) at the largest frame the settings allow; the encode kernel's
+ * packer writes there at absolute positions, round after round, and its state stays in HBM.  A round
+ * (lamehip_batch_encode_available / _finish) is then the append / conversion / gain launches, the encode launch -- in
+ * windows or on the fused kernel as any incremental round -- and three small launches of csrc/lh_drain.hip: no LhFrameOut
+ * record comes home and no host packer runs.  The drain kernels find, per stream, the position P up to which the slice is
+ * what lame_encode_buffer would have returned: the packer's cursor -- or, when a frame's main data ended exactly on the
+ * start of a header that is already queued, that header's start: the reference writes a header only with the next bit
+ * behind it, the device packer steps over it at once (digital silence does this frame after frame) --, and after
+ * lamehip_batch_finish the end of the last frame.  They gather [drained, P) of every slice into one round buffer, every
+ * stream on a 16-byte boundary; a table (offset, count, status) per stream comes home first, then ONE copy of exactly the
+ * round's bytes into pinned memory, then the round's wait.  A stream the caller has not drained is gathered again with the
+ * next round: the pinned buffer always holds everything undrained.  A stream whose packer reports a status makes the round
+ * return LAMEHIP_ERR_PAYLOAD (lamehip_last_error() names the stream).  lamehip_batch_reset starts the batch over.
+ * Off (the default): launches, layouts and bytes of every path are what they were. */
+int     lamehip_batch_set_incremental_packing(lamehip_batch *, int on);
+/* the bytes lamehip_batch_drain would copy, in place: on a batch with lamehip_batch_set_incremental_packing in the round's
+ * pinned buffer, else in a buffer of the batch's.  Valid until the next lamehip_batch_encode_available, _finish or _reset
+ * (host packer: or the stream's next _drain_ptr).  Returns their number (0: nothing new, *bytes NULL) or -1; counts as a
+ * drain. */
+long    lamehip_batch_drain_ptr(lamehip_batch *, int stream, const unsigned char **bytes);
+/* HIP-event time in ms of the drain kernels of the last lamehip_batch_encode_available / _finish of a batch with
+ * lamehip_batch_set_incremental_packing; 0 when none ran.  Not part of lamehip_batch_last_kernel_ms / _parts_ms. */
+float   lamehip_batch_last_drain_ms(lamehip_batch *);
 /* encode every stream completely (all frames incl. the flush frames), payload
  * stays in HBM; asynchronous on the batch's HIP stream */
 int     lamehip_batch_encode(lamehip_batch *);
@@ -463,7 +498,8 @@ long    lamehip_batch_get_bytes_tagged(lamehip_batch *, int stream, unsigned cha
  * The images are those of lamehip_batch_pack_tagged, byte for byte (a radio gain measured by lamehip_batch_set_replaygain is
  * put into the image when it is handed out); when the tag does not fit a frame they are the audio alone, as there.
  * lamehip_batch_get_bytes / _get_bytes_all / _bytes_ptr return the audio alone, as before.  Returns -1 unless the batch packs
- * on the device (lamehip_batch_set_device_packing first) and on an incremental batch; a failed allocation returns
+ * on the device (lamehip_batch_set_device_packing first), on an incremental batch and behind
+ * lamehip_batch_set_incremental_packing; a failed allocation returns
  * LAMEHIP_ERR_DEVICE and leaves the batch as it was.  Off (the default): launches, layouts and bytes are what they were. */
 int     lamehip_batch_set_device_tagging(lamehip_batch *, int on);
 long    lamehip_batch_image_ptr(lamehip_batch *, int stream, const unsigned char **image);
