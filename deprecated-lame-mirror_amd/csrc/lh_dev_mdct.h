@@ -362,6 +362,9 @@ lh_mdct_long(float *out, float const *in)
     }
 }
 
+/* (lh_subband.hip, whose LDS image holds two granules of sub-band samples where the window lay and none of the one before,
+ * brings its own versions of the two stages below: LH_CUSTOM_MDCT_STAGES) */
+#ifndef LH_CUSTOM_MDCT_STAGES
 /* polyphase filtering of the 36 slots of the current frame window of channel
  * `ch' into sb[1..2]; one wave (reference newmdct.c:958-973, 984-991) */
 LH_STAGEFN void
@@ -491,5 +494,6 @@ lh_mdct_granules(int ch)
     }
     LH_WAVE_SYNC();
 }
+#endif                          /* !LH_CUSTOM_MDCT_STAGES */
 
 #endif
