@@ -34,6 +34,9 @@ extern "C" int lh_launch_tag(const LhTagParams * p, const LhStreamDesc * descs, 
 extern "C" int lh_launch_drain(const LhDrainParams * p, const LhStreamDesc * descs, const LhStreamState * states, const long long *drained,
                                long long *carry, const unsigned char *pool, LhDrainRow * rows, int nstreams, const LhDrainTile * tiles,
                                long long ntiles, unsigned char *round, long long round_cap, void *stream);
+extern "C" int lh_launch_tag_resume(const LhTagParams * p, const LhTagPow * pw, const LhStreamDesc * descs, const LhStreamState * states,
+                                    const LhDrainRow * rows, const LhFrameOut * out, const unsigned char *pool, const unsigned char *tmpl,
+                                    const int *padding, LhTagCarry * carry, unsigned char *tags, int final, int nstreams, void *stream);
 
 /* per device: the end of the last launch that filled it (lamehip_batch_encode) */
 static LhLaunchSerial &
@@ -236,6 +239,22 @@ struct lamehip_batch {
     LhEvent ev_dr[2];
     int     dr_ran = 0;         /* the last round launched the drain kernels (between ev_dr[0] and ev_dr[1]) */
     float   dr_ms = 0;
+    /* ... with tag frames (lamehip_batch_set_incremental_tagging): a carry per stream in HBM (lh_tag.h: LhTagCarry) that ONE
+     * launch of lh_tag_resume_kernel moves on behind every round's drain -- the music CRC over the bytes that became final,
+     * the seek table's bookkeeping over the round's records --; the final round's launch makes the frames of it, which come
+     * home to h_tg_tags behind the table, out of which lamehip_batch_tag_ptr / _get_tags_all hand them */
+    int     inc_tag = 0;
+    int     tg_have = 0;        /* h_tg_tags holds the final round's frames (and h_dr_rows their streams' statuses) */
+    LhTagParams tg_p = {};      /* (total 0: the tag does not fit a frame, nothing is launched) */
+    LhDevBuf < LhTagCarry > d_tg_carry;
+    LhDevBuf < LhTagPow > d_tg_pow;
+    LhDevBuf < unsigned char >d_tg_tmpl, d_tg_tags;
+    LhDevBuf < int >d_tg_pad;
+    std::vector < int >h_tg_pad;        /* the end padding per stream, as the final round's kernel read it */
+    LhPinned < unsigned char >h_tg_tags;        /* [B][tg_p.total] */
+    std::vector < char >tg_patched;     /* stream s's frame in h_tg_tags carries its gain */
+    LhEvent ev_tg[2];
+    int     tg_ran = 0;         /* the last round launched the tag kernel (between ev_tg[0] and ev_tg[1]) */
     std::vector < std::vector < unsigned char > >handed;        /* host packer: what lamehip_batch_drain_ptr last handed out */
     /* typed and device-resident appends (lamehip_batch_append_input / _append_input_device / _append_device): the table of
      * segments lh_append_kernel works through, pinned and in HBM -- entries [0, LH_STAGE_SEGS) for the chunks staged in the
@@ -1092,6 +1111,14 @@ batch_drain_begin(lamehip_batch * b)
     long long const slice = (long long) lh_total_frames_fs(b->inc_rs ? b->capf : b->cap, fs_of(b->cfg)) * frame_max;
     HIPCHK(b->d_bytes.reserve((size_t) b->B * (size_t) slice));
     HIPCHK(hipMemsetAsync(b->d_dr_carry.get(), 0, (size_t) b->B * sizeof(long long), b->stream));
+    if (b->inc_tag) {
+        /* (with tag frames: every stream's carry in front of its first byte and frame, no frame to hand out) */
+        HIPCHK(hipMemsetAsync(b->d_tg_carry.get(), 0, (size_t) b->B * sizeof(LhTagCarry), b->stream));
+        b->tg_patched.assign((size_t) b->B, 0);
+        b->tg_have = 0;
+        b->tg_ran = 0;
+        b->tag_ms = 0;
+    }
     b->dr_slice = slice;
     b->dr_frame_max = frame_max;
     b->dr_drained.assign((size_t) b->B, 0);
@@ -1793,8 +1820,34 @@ batch_drain_plan(lamehip_batch * b, const std::vector < int >&upto)
     return 0;
 }
 
+/* A round's tag launch (lamehip_batch_set_incremental_tagging), behind the drain's launches -- its table in HBM says which
+ * bytes are final -- between ev_tg[0] and ev_tg[1].  The final round brings what the kernel cannot know, every stream's end
+ * padding: the figure the one-shot tagged path uses for a stream of that many samples, or the conversion's. */
+static int
+batch_tag_launch(lamehip_batch * b, int end)
+{
+    b->tg_ran = 0;
+    if (!b->inc_tag || b->tg_p.total <= 0)
+        return 0;
+    if (end) {
+        for (int s = 0; s < b->B; s++)
+            b->h_tg_pad[(size_t) s] = batch_padding(b, s);
+        HIPCHK(hipMemcpyAsync(b->d_tg_pad.get(), b->h_tg_pad.data(), (size_t) b->B * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    }
+    HIPCHK(hipEventRecord(b->ev_tg[0], b->stream));
+    int const rc = lh_launch_tag_resume(&b->tg_p, b->d_tg_pow.get(), (const LhStreamDesc *) b->d_stage.get(), b->d_state.get(),
+                                        b->d_dr_rows.get(), b->d_out.get(), b->d_bytes.get(), b->d_tg_tmpl.get(), b->d_tg_pad.get(),
+                                        b->d_tg_carry.get(), b->d_tg_tags.get(), end, b->B, (void *) (hipStream_t) b->stream);
+    if (rc)
+        return set_err("tag launch", (hipError_t) rc);
+    HIPCHK(hipEventRecord(b->ev_tg[1], b->stream));
+    b->tg_ran = 1;
+    return 0;
+}
+
 /* ... and behind its encode launch: the table of tiles and `drained' to HBM, the three drain launches between ev_dr[0] and
- * ev_dr[1], and the table on its way home */
+ * ev_dr[1], the tag launch of a batch that carries tag frames, and the table on its way home -- behind it, in the final
+ * round, the tag frames */
 static int
 batch_drain_launch(lamehip_batch * b, int end)
 {
@@ -1819,7 +1872,14 @@ batch_drain_launch(lamehip_batch * b, int end)
         return set_err("drain launch", (hipError_t) rc);
     HIPCHK(hipEventRecord(b->ev_dr[1], b->stream));
     b->dr_ran = 1;
+    {
+        int const tr = batch_tag_launch(b, end);
+        if (tr)
+            return tr;
+    }
     HIPCHK(hipMemcpyAsync(b->h_dr_rows.get(), b->d_dr_rows.get(), ((size_t) b->B + 1) * sizeof(LhDrainRow), hipMemcpyDeviceToHost, b->stream));
+    if (end && b->tg_ran)
+        HIPCHK(hipMemcpyAsync(b->h_tg_tags.get(), b->d_tg_tags.get(), (size_t) b->B * (size_t) b->tg_p.total, hipMemcpyDeviceToHost, b->stream));
     return 0;
 }
 
@@ -1827,7 +1887,7 @@ batch_drain_launch(lamehip_batch * b, int end)
  * round's wait.  A stream whose packer reported a status -- or whose position the drain could not place in its slice --
  * fails the round with LAMEHIP_ERR_PAYLOAD; the other streams' bytes are there. */
 static int
-batch_drain_home(lamehip_batch * b)
+batch_drain_home(lamehip_batch * b, int end)
 {
     const LhDrainRow *rows = b->h_dr_rows.get();
     long long const total = rows[b->B].off;
@@ -1835,6 +1895,16 @@ batch_drain_home(lamehip_batch * b)
     if (b->dr_ran && hipEventElapsedTime(&b->dr_ms, b->ev_dr[0], b->ev_dr[1]) != hipSuccess) {
         (void) hipGetLastError();
         b->dr_ms = 0;
+    }
+    if (b->inc_tag) {
+        /* (the tag launch's time; the final round's frames came home behind the table, which the caller has waited for) */
+        b->tag_ms = 0;
+        if (b->tg_ran && hipEventElapsedTime(&b->tag_ms, b->ev_tg[0], b->ev_tg[1]) != hipSuccess) {
+            (void) hipGetLastError();
+            b->tag_ms = 0;
+        }
+        if (end && b->tg_ran)
+            b->tg_have = 1;
     }
     if (total < 0 || total > b->dr_padded) {
         snprintf(g_err, sizeof(g_err), "incremental packing: the drain found %lld bytes where the round's bound is %lld", total, b->dr_padded);
@@ -1915,6 +1985,10 @@ batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
         return rc;
     if (total == 0) {
         b->dr_ms = 0;           /* (no drain either: what the last round brought home stays where it is) */
+        if (b->inc_tag) {
+            b->tg_ran = 0;      /* (and no tag launch) */
+            b->tag_ms = 0;
+        }
         HIPCHK(hipStreamSynchronize(b->stream));
         batch_append_time(b);
         batch_tiles_done(b);
@@ -1941,7 +2015,7 @@ batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
         batch_append_time(b);
         batch_tiles_done(b);
         batch_gain_round_done(b, end);
-        if ((rc = batch_drain_home(b)) == 0)
+        if ((rc = batch_drain_home(b, end)) == 0)
             rc = batch_drain_done(b, upto);
         for (int s = 0; s < b->B; s++)
             if (upto[(size_t) s] > b->done[(size_t) s])
@@ -3067,6 +3141,7 @@ lamehip_batch_set_device_packing(lamehip_batch * b, int on)
     if (!b->dev_pack) {
         b->dev_tag = 0;         /* (the tag frames go in front of the device packer's bytes) */
         b->inc_pack = 0;        /* (and the rounds of an incremental batch are the device packer's) */
+        b->inc_tag = 0;         /* (and so are their tag frames) */
     }
     return 0;
 }
@@ -3075,8 +3150,8 @@ lamehip_batch_set_device_packing(lamehip_batch * b, int on)
  * every lamehip_batch_encode_available / _finish runs the encode kernel with its bit packer on every stream's fixed slice of
  * the byte pool and, behind it, the drain kernels (lh_drain.hip), and lamehip_batch_drain / _drain_ptr hand out finished MP3
  * bytes that came home in one copy -- no LhFrameOut record crosses to the host and no host packer runs.  Only before any PCM
- * is handed over; not with device tagging (an incremental batch has no tagged output); lamehip_batch_set_incremental_resampling
- * and _replaygain go on top when called after it.  on = 0 puts the batch back as it was. */
+ * is handed over; not with device tagging (an incremental batch's tag frames are lamehip_batch_set_incremental_tagging's);
+ * lamehip_batch_set_incremental_resampling, _replaygain and _tagging go on top when called after it.  on = 0 puts the batch back as it was. */
 extern "C" int
 lamehip_batch_set_incremental_packing(lamehip_batch * b, int on)
 {
@@ -3101,6 +3176,11 @@ lamehip_batch_set_incremental_packing(lamehip_batch * b, int on)
         if (!on && b->inc_pack && (b->inc_rs || b->inc_rg)) {
             snprintf(g_err, sizeof(g_err), "lamehip_batch_set_incremental_packing: lamehip_batch_set_incremental_resampling / _replaygain "
                      "were switched on on top of it; switch them off first");
+            return -1;
+        }
+        if (!on && b->inc_pack && b->inc_tag) {
+            snprintf(g_err, sizeof(g_err), "lamehip_batch_set_incremental_packing: lamehip_batch_set_incremental_tagging was switched on "
+                     "on top of it; switch it off first");
             return -1;
         }
         b->inc_pack = on != 0 && b->inc_pack;
@@ -3229,6 +3309,184 @@ extern "C" float
 lamehip_batch_last_tag_ms(lamehip_batch * b)
 {
     return b ? b->tag_ms : 0.0f;
+}
+
+/* Tag frames for an incremental batch that packs on the device (lamehip_batch_set_incremental_packing first): behind every
+ * round's drain one more launch (lh_tag.hip: lh_tag_resume_kernel) moves a carry per stream on -- the music CRC over the
+ * bytes that became final with the round, lh_tag_add_frame's bookkeeping over the round's records --, the final round's
+ * launch makes every stream's Xing/Info + LAME frame of it, and the frames come home behind the final round's table
+ * (lamehip_batch_tag_ptr / _get_tags_all).  The drains hand out what they handed out.  Only before any PCM is handed over;
+ * on = 0 puts the batch back as it was. */
+extern "C" int
+lamehip_batch_set_incremental_tagging(lamehip_batch * b, int on)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b)
+        return -1;
+    if (!b->inc_pack) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_incremental_tagging: for a batch that packs its rounds on the device "
+                 "(lamehip_batch_set_incremental_packing first)");
+        return -1;
+    }
+    if (b->pcm_given || b->encoded || b->incremental) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_incremental_tagging: only before any PCM is handed over");
+        return -1;
+    }
+    if (!on || b->inc_tag) {
+        b->inc_tag = on != 0 && b->inc_tag;
+        return 0;
+    }
+    /* everything new first: a failure leaves the batch as it was */
+    LhVbrTag v;
+    LhTagParams p;
+    LhTagPow pw;
+    int const total = lh_tag_init(&v, &b->cfg);
+    if (b->rate_in)
+        v.samplerate_in = b->rate_in;
+    lh_tag_params(&v, &b->cfg, &p);
+    lh_tag_pow_table(&pw);
+    size_t const room = (size_t) b->B * (size_t) (total > 0 ? total : 1);
+    LhDevBuf < LhTagCarry > carry;
+    LhDevBuf < LhTagPow > powers;
+    LhDevBuf < unsigned char >tmpl, tags;
+    LhDevBuf < int >pad;
+    LhPinned < unsigned char >h_tags;
+    LhEvent ev[2];
+    std::vector < int >h_pad;
+    std::vector < char >patched;
+    std::vector < unsigned char >h_tmpl((size_t) (total > 0 ? total : 1), 0);
+    if (total > 0)
+        lh_tag_template(&v, &b->cfg, b->cfg.vbr_q, h_tmpl.data());
+    hipError_t e = carry.alloc((size_t) b->B);
+    if (e == hipSuccess)
+        e = powers.alloc(1);
+    if (e == hipSuccess)
+        e = tmpl.alloc(h_tmpl.size());
+    if (e == hipSuccess)
+        e = tags.alloc(room);
+    if (e == hipSuccess)
+        e = pad.alloc((size_t) b->B);
+    if (e == hipSuccess)
+        e = h_tags.alloc(room);
+    if (e == hipSuccess)
+        e = ev[0].create();
+    if (e == hipSuccess)
+        e = ev[1].create();
+    if (e == hipSuccess)
+        e = hipMemset(carry.get(), 0, (size_t) b->B * sizeof(LhTagCarry));
+    if (e == hipSuccess)
+        e = hipMemset(tags.get(), 0, room);
+    if (e == hipSuccess)
+        e = hipMemset(pad.get(), 0, (size_t) b->B * sizeof(int));
+    if (e == hipSuccess)
+        e = hipMemcpy(powers.get(), &pw, sizeof(pw), hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(tmpl.get(), h_tmpl.data(), h_tmpl.size(), hipMemcpyHostToDevice);
+    try {
+        h_pad.assign((size_t) b->B, 0);
+        patched.assign((size_t) b->B, 0);
+    }
+    catch(const std::bad_alloc &) {
+        e = hipErrorOutOfMemory;
+    }
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        return set_err("lamehip_batch_set_incremental_tagging: allocation", e);
+    }
+    memset(h_tags.get(), 0, room);
+    b->d_tg_carry = std::move(carry);
+    b->d_tg_pow = std::move(powers);
+    b->d_tg_tmpl = std::move(tmpl);
+    b->d_tg_tags = std::move(tags);
+    b->d_tg_pad = std::move(pad);
+    b->h_tg_tags = std::move(h_tags);
+    b->ev_tg[0] = std::move(ev[0]);
+    b->ev_tg[1] = std::move(ev[1]);
+    b->h_tg_pad = std::move(h_pad);
+    b->tg_patched = std::move(patched);
+    b->tg_p = p;
+    b->tg_have = 0;
+    b->tg_ran = 0;
+    b->inc_tag = 1;
+    return 0;
+}
+
+/* the tag frame's length for the batch's settings; 0 when the tag does not fit a frame, or the switch is off */
+extern "C" int
+lamehip_batch_tag_size(lamehip_batch * b)
+{
+    return (b && b->inc_tag) ? b->tg_p.total : 0;
+}
+
+/* who: one of the tag getters of an incremental batch */
+static int
+batch_tags_ready(lamehip_batch * b, const char *who)
+{
+    if (!b)
+        return -1;
+    if (!b->inc_tag) {
+        snprintf(g_err, sizeof(g_err), "%s: lamehip_batch_set_incremental_tagging is not on", who);
+        return -1;
+    }
+    /* (a final round has brought them home; a batch whose tag does not fit a frame has none to bring) */
+    if (!(b->tg_p.total > 0 ? b->tg_have : b->finished)) {
+        snprintf(g_err, sizeof(g_err), "%s: an incremental batch's tag frames exist after lamehip_batch_finish", who);
+        return -1;
+    }
+    return 0;
+}
+
+/* stream s's frame in the pinned buffer, its radio gain put in (once) when the batch measured one round by round; returns
+ * its length or a negative code */
+static long
+batch_tag_at(lamehip_batch * b, int s, unsigned char **at)
+{
+    int const total = b->tg_p.total;
+    *at = nullptr;
+    if (total <= 0)
+        return 0;
+    if (b->h_dr_rows.get()[s].status != 0) {
+        snprintf(g_err, sizeof(g_err), "device bit packer reported status %d for stream %d", b->h_dr_rows.get()[s].status, s);
+        return LAMEHIP_ERR_PAYLOAD;
+    }
+    *at = b->h_tg_tags.get() + (size_t) s * (size_t) total;
+    if (b->inc_rg && b->rg_closed && !b->tg_patched[(size_t) s]) {
+        lh_tag_patch_gain(*at, b->tg_p.at, b->rg_tenths[(size_t) s]);
+        b->tg_patched[(size_t) s] = 1;
+    }
+    return total;
+}
+
+/* stream s's final tag frame in the batch's pinned buffer (valid until lamehip_batch_reset): returns its length, or a
+ * negative code */
+extern "C" long
+lamehip_batch_tag_ptr(lamehip_batch * b, int s, const unsigned char **frame)
+{
+    unsigned char *at = nullptr;
+    if (!b || s < 0 || s >= b->B || !frame || batch_tags_ready(b, "lamehip_batch_tag_ptr") != 0)
+        return -1;
+    long const n = batch_tag_at(b, s, &at);
+    *frame = at;
+    return n;
+}
+
+/* all streams' tag frames: stream s at out + s * out_stride, sizes[s] = bytes or a negative code */
+extern "C" int
+lamehip_batch_get_tags_all(lamehip_batch * b, unsigned char *out, long out_stride, long *sizes)
+{
+    int     bad = 0;
+    if (!out || !sizes || batch_tags_ready(b, "lamehip_batch_get_tags_all") != 0)
+        return -1;
+    for (int s = 0; s < b->B; s++) {
+        unsigned char *at = nullptr;
+        long    n = b->tg_p.total > out_stride ? -1 : batch_tag_at(b, s, &at);
+        sizes[s] = n;
+        if (n < 0)
+            bad++;
+        else if (n > 0)
+            memcpy(out + (size_t) s * (size_t) out_stride, at, (size_t) n);
+    }
+    return bad ? -1 : 0;
 }
 
 /* Device tagging: the radio gain into stream s's image (tag frame first), which the kernel wrote with the field zero -- the

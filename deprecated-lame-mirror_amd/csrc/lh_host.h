@@ -148,6 +148,8 @@ int     lh_tag_frame(const LhVbrTag * v, const LhConfig * c, int vbr_q, int enc_
  * kernel of a device-packed batch (lh_tag.hip) needs besides it; the second half is lh_tag.h's, host and device */
 void    lh_tag_template(const LhVbrTag * v, const LhConfig * c, int vbr_q, unsigned char *buf);
 void    lh_tag_params(const LhVbrTag * v, const LhConfig * c, LhTagParams * p);
+/* ... and what the tag kernel of an incremental batch needs on top: the advance matrices by powers of two */
+void    lh_tag_pow_table(LhTagPow * t);
 int     lh_end_padding(long nsamples);
 int     lh_end_padding_fs(long nsamples, int samples_per_frame);
 

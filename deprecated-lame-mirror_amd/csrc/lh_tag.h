@@ -68,6 +68,30 @@ typedef struct LhTagParams {
     uint16_t adv[LH_TAG_NADV][16];
 } LhTagParams;
 
+/* An incremental batch that packs on the device (lamehip_batch_set_incremental_tagging): what a stream's tag carries from
+ * round to round in HBM, all zero at first.  lh_tag_resume_kernel moves it on behind every round's drain: the music CRC
+ * over the bytes that are final, the bookkeeping of lh_tag_add_frame over the round's records; behind the flush it makes
+ * the frame of it. */
+typedef struct LhTagCarry {
+    long long crc_upto;         /* bytes of the slice the CRC covers: [0, crc_upto) */
+    uint32_t crc;               /* the music CRC over them */
+    int     frames;             /* frames seen */
+    int     want;               /* the bag's sampling distance (0 counts as 1: no frame yet) */
+    int     pos;                /* samples in the bag */
+    int     sum;                /* the frames' bit rates added up */
+    int     mode_ext;           /* the last frame's */
+    int     bad;                /* a round found a status, or a position that does not continue the last one: no tag */
+    int     pad;
+    int     bag[LH_TAG_BAG_SIZE];
+} LhTagCarry;
+
+/* the music CRC moved on over a run of 1 << k zero bytes, k = 0 .. LH_TAG_NPOW - 1, 16 columns each: a run of any length
+ * is the runs of its set bits one after the other (lh_tag_crc_advance_by).  Made on the host (lh_tag_pow_table). */
+#define LH_TAG_NPOW 40
+typedef struct LhTagPow {
+    uint16_t col[LH_TAG_NPOW][16];
+} LhTagPow;
+
 /* one byte into the music CRC (reflected polynomial 0xA001, reference VbrTag.c:73-122) without a table: the byte's eight
  * steps shift its bits out through taps 0, 13 and 15 -- each bit lands 6 and 7 places up, and their parity on both ends */
 LH_TAG_FN uint32_t
@@ -87,6 +111,27 @@ lh_tag_crc_advance(uint32_t crc, const uint16_t *col)
     for (k = 0; k < 16; k++)
         out ^= (0u - ((crc >> k) & 1u)) & col[k];
     return out;
+}
+
+/* ... over a run of n zero bytes, n >= 0: through the set bits of n */
+LH_TAG_FN uint32_t
+lh_tag_crc_advance_by(uint32_t crc, const LhTagPow * t, long long n)
+{
+    int     k;
+    for (k = 0; k < LH_TAG_NPOW && (n >> k) != 0; k++)
+        if ((n >> k) & 1)
+            crc = lh_tag_crc_advance(crc, t->col[k]);
+    return crc;
+}
+
+/* the bag's sampling distance after n frames: the smallest power of two with n / want < LH_TAG_BAG_SIZE */
+LH_TAG_FN int
+lh_tag_want(int n)
+{
+    int     w = 1;
+    while (n / w >= LH_TAG_BAG_SIZE)
+        w += w;
+    return w;
 }
 
 /* CRC-16 of a frame's protected part (lh_header_crc of lh_bitstream.c, which the host packer keeps for itself) */

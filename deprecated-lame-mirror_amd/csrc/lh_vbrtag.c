@@ -282,6 +282,19 @@ lh_tag_params(const LhVbrTag * v, const LhConfig * c, LhTagParams * p)
         }
 }
 
+/* The advance matrices of an incremental batch's tag kernel (lh_tag.h: LhTagPow): a byte's step for k = 0, and every
+ * further one the one before applied to itself -- a run of 2 << k zeros is a run of 1 << k twice. */
+void
+lh_tag_pow_table(LhTagPow * t)
+{
+    int     j, k;
+    for (k = 0; k < 16; k++)
+        t->col[0][k] = (uint16_t) lh_tag_crc_byte(1u << k, 0);
+    for (j = 1; j < LH_TAG_NPOW; j++)
+        for (k = 0; k < 16; k++)
+            t->col[j][k] = (uint16_t) lh_tag_crc_advance(t->col[j - 1][k], t->col[j - 1]);
+}
+
 /* final tag frame; returns the frame size, 0 when there is no tag (reference VbrTag.c:900-1018): the template, finished
  * with the stream's own fields (lh_tag.h).  vbr_q is the caller-level setting the "quality" byte is made of. */
 int

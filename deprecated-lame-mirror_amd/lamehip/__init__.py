@@ -497,8 +497,45 @@ class Batch:
         n = C.c_longlong(0)
         return self.lib.lamehip_batch_bytes_device_ptr(self.b, C.byref(n)), int(n.value)
 
+    def set_incremental_tagging(self, on=True):
+        """Tag frames for an incremental batch on the device packer (set_incremental_packing() first, before any PCM): every
+        round moves a carry per stream on in HBM (csrc/lh_tag.hip: lh_tag_resume_kernel), finish() brings every stream's
+        final Xing/Info + LAME frame home -- tag(), tags_all().  The drains are unchanged: the caller keeps tag_size()
+        bytes free at the head of the file."""
+        self.lib.lamehip_batch_set_incremental_tagging.argtypes = [C.c_void_p, C.c_int]
+        rc = self.lib.lamehip_batch_set_incremental_tagging(self.b, 1 if on else 0)
+        if rc:
+            raise RuntimeError("lamehip_batch_set_incremental_tagging failed (%d): %s" % (rc, last_error()))
+
+    def tag_size(self):
+        """The tag frame's length (set_incremental_tagging()); 0: the tag does not fit a frame, or the switch is off."""
+        self.lib.lamehip_batch_tag_size.argtypes = [C.c_void_p]
+        return int(self.lib.lamehip_batch_tag_size(self.b))
+
+    def tag(self, s):
+        """Stream s's final tag frame after finish() (set_incremental_tagging()), as bytes."""
+        self.lib.lamehip_batch_tag_ptr.restype = C.c_long
+        self.lib.lamehip_batch_tag_ptr.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        p = C.c_void_p()
+        k = self.lib.lamehip_batch_tag_ptr(self.b, s, C.byref(p))
+        if k < 0:
+            raise RuntimeError("lamehip_batch_tag_ptr failed (%d): %s" % (k, last_error()))
+        return C.string_at(p.value, k) if k > 0 else b""
+
+    def tags_all(self):
+        """(buffer [B, tag_size()] uint8, sizes) of the streams' tag frames after finish()."""
+        stride = max(self.tag_size(), 1)
+        out = np.zeros((self.n, stride), dtype=np.uint8)
+        sizes = np.zeros(self.n, dtype=np.int64)
+        self.lib.lamehip_batch_get_tags_all.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]
+        rc = self.lib.lamehip_batch_get_tags_all(self.b, out.ctypes.data, stride, sizes.ctypes.data)
+        if rc:
+            raise RuntimeError("lamehip_batch_get_tags_all failed (%d): %s" % (rc, last_error()))
+        return out, sizes
+
     def tag_ms(self):
-        """HIP-event time of the last encode()'s tag kernel, 0 when none ran."""
+        """HIP-event time of the last encode()'s tag kernel -- with set_incremental_tagging(): of the tag launch of the last
+        encode_available() / finish() --, 0 when none ran."""
         self.lib.lamehip_batch_last_tag_ms.restype = C.c_float
         self.lib.lamehip_batch_last_tag_ms.argtypes = [C.c_void_p]
         return float(self.lib.lamehip_batch_last_tag_ms(self.b))

@@ -346,7 +346,8 @@ int     lamehip_batch_set_replaygain(lamehip_batch *, int on);
  * either).  lamehip_batch_reset clears carried state, windows and gains.  An append whose stream, flushed right after the
  * call, would be longer than the analysis takes (0x7fffff00 samples) is refused: -1, nothing counted, the error names the
  * call.  Until the first append the batch behaves as one with lamehip_batch_set_replaygain(b, 1): whole streams through
- * lamehip_batch_encode.  An incremental batch has no tagged output, so the gain is not written into a tag. */
+ * lamehip_batch_encode.  An incremental batch writes the gain into a tag only through lamehip_batch_set_incremental_tagging:
+ * lamehip_batch_tag_ptr / _get_tags_all put it into the frame they hand out. */
 int     lamehip_batch_set_incremental_replaygain(lamehip_batch *, int on);
 /* stream's radio gain in tenths of a dB (0 when not one 50 ms window was completed); waits for the batch's stream.  -1
  * before a lamehip_batch_encode with the switch on, and again after lamehip_batch_reset; on an incremental batch -1 before
@@ -415,8 +416,8 @@ int     lamehip_batch_append_device(lamehip_batch *, const void *dev, long long 
 float   lamehip_batch_last_append_ms(lamehip_batch *);
 /* Incremental use on the device bit packer.  Accepted only with lamehip_batch_set_device_packing on (-1 otherwise,
  * lamehip_last_error() names that call), only before any PCM, length, mirror or append has been handed over, and not with
- * lamehip_batch_set_device_tagging on (an incremental batch has no tagged output; device tagging is refused behind it
- * likewise).  on = 0 before the first append puts the batch back as it was: a device-packed batch that refuses every
+ * lamehip_batch_set_device_tagging on (device tagging puts the tag frame in front of a whole stream's bytes and is refused
+ * behind it likewise; an incremental batch gets its tag frames from lamehip_batch_set_incremental_tagging).  on = 0 before the first append puts the batch back as it was: a device-packed batch that refuses every
  * append.  An allocation failure returns LAMEHIP_ERR_DEVICE and leaves the batch as it was.  With it on,
  * lamehip_batch_append, _append_input, _append_input_device and _append_device are accepted, and
  * lamehip_batch_set_incremental_resampling / _set_incremental_replaygain may be switched on behind it (both run in front of
@@ -499,14 +500,44 @@ long    lamehip_batch_get_bytes_tagged(lamehip_batch *, int stream, unsigned cha
  * put into the image when it is handed out); when the tag does not fit a frame they are the audio alone, as there.
  * lamehip_batch_get_bytes / _get_bytes_all / _bytes_ptr return the audio alone, as before.  Returns -1 unless the batch packs
  * on the device (lamehip_batch_set_device_packing first), on an incremental batch and behind
- * lamehip_batch_set_incremental_packing; a failed allocation returns
+ * lamehip_batch_set_incremental_packing (whose tag frames are lamehip_batch_set_incremental_tagging's); a failed allocation returns
  * LAMEHIP_ERR_DEVICE and leaves the batch as it was.  Off (the default): launches, layouts and bytes are what they were. */
 int     lamehip_batch_set_device_tagging(lamehip_batch *, int on);
 long    lamehip_batch_image_ptr(lamehip_batch *, int stream, const unsigned char **image);
 int     lamehip_batch_get_images_all(lamehip_batch *, unsigned char *out, long out_stride, long *sizes);
 /* HIP-event time of the tag kernel of the last lamehip_batch_encode in ms (after lamehip_batch_sync; events of its own: not
- * part of lamehip_batch_last_kernel_ms or of its parts); 0 when the kernel did not run */
+ * part of lamehip_batch_last_kernel_ms or of its parts); 0 when the kernel did not run.  On a batch with
+ * lamehip_batch_set_incremental_tagging: of the tag launch of the last lamehip_batch_encode_available / _finish. */
 float   lamehip_batch_last_tag_ms(lamehip_batch *);
+/* Tag frames for an incremental batch that packs on the device.  Accepted only with lamehip_batch_set_incremental_packing on
+ * and only before any PCM, length, mirror or append has been handed over (-1 otherwise, lamehip_last_error() names the call);
+ * on = 0 before the first append puts the batch back as it was; an allocation failure returns LAMEHIP_ERR_DEVICE and leaves
+ * the batch as it was.  While it is on, lamehip_batch_set_incremental_packing(b, 0) is refused.
+ * Every stream carries a small record in HBM (csrc/lh_tag.h: LhTagCarry): the music CRC over the bytes of its slice that
+ * are final, and lh_tag_add_frame's bookkeeping -- frames, the bag of seek points, its sampling distance, the sum, the last
+ * frame's mode extension.  Behind every round's drain launches ONE more launch (csrc/lh_tag.hip: lh_tag_resume_kernel, a
+ * workgroup per stream) moves it on: the CRC over the round's new final bytes [crc_upto, P) -- read once, in the round they
+ * become final --, joined to the carried one, and the round's LhFrameOut records into the bag.  A stream the round brought
+ * nothing leaves at once; a round without a complete frame makes no launch.  Behind the flush the kernel makes every stream's
+ * final Xing/Info + LAME frame from the carry, and the frames come home to pinned memory with the final round's table.
+ * The drains are unchanged: they hand out the audio bytes lame_encode_buffer returns with bWriteVbrTag off, no placeholder.
+ * The caller reserves lamehip_batch_tag_size bytes at the head of the file, as the reference's frontend does with its zero
+ * frame, and writes the tag there at the end:
+ *   lamehip_batch_tag_size       the frame's length for the batch's settings, constant from the moment the switch is on; 0
+ *                                when the tag does not fit a frame (the batch then has no tags, as on the one-shot path) or
+ *                                the switch is off
+ *   lamehip_batch_tag_ptr        after lamehip_batch_finish: stream's final tag frame in place in the pinned buffer (valid
+ *                                until lamehip_batch_reset), returns its length; -1 before lamehip_batch_finish,
+ *                                LAMEHIP_ERR_PAYLOAD for a stream whose packer or drain reported a status
+ *   lamehip_batch_get_tags_all   frame s at out + s * out_stride, sizes[s] = bytes or a negative code
+ * The frame is, byte for byte, the one lamehip_batch_pack_tagged / _get_bytes_tagged put in front of the same stream on a
+ * one-shot batch fed the same samples.  With lamehip_batch_set_incremental_replaygain on, the radio gain is put into the frame
+ * when it is handed out.  lamehip_batch_reset zeroes the carry.  Off (the default): launches, layouts and bytes of every path
+ * are what they were. */
+int     lamehip_batch_set_incremental_tagging(lamehip_batch *, int on);
+int     lamehip_batch_tag_size(lamehip_batch *);
+long    lamehip_batch_tag_ptr(lamehip_batch *, int stream, const unsigned char **frame);
+int     lamehip_batch_get_tags_all(lamehip_batch *, unsigned char *out, long out_stride, long *sizes);
 /* test accessor: the device packer's byte pool in HBM as the last lamehip_batch_reserve / lamehip_batch_encode left it (with
  * device tagging the tag frames' room is part of it) and its size in bytes; NULL when there is none */
 void   *lamehip_batch_bytes_device_ptr(lamehip_batch *, long long *size);
