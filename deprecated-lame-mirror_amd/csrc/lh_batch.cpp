@@ -37,6 +37,8 @@ extern "C" int lh_launch_drain(const LhDrainParams * p, const LhStreamDesc * des
 extern "C" int lh_launch_tag_resume(const LhTagParams * p, const LhTagPow * pw, const LhStreamDesc * descs, const LhStreamState * states,
                                     const LhDrainRow * rows, const LhFrameOut * out, const unsigned char *pool, const unsigned char *tmpl,
                                     const int *padding, LhTagCarry * carry, unsigned char *tags, int final, int nstreams, void *stream);
+extern "C" int lh_launch_slot_restart(const int *list, int nlist, int nstreams, LhStreamState * states, const LhStreamState * states0,
+                                      long long *drain_carry, LhTagCarry * tag_carry, LhGainCarry * gain_carry, void *stream);
 
 /* per device: the end of the last launch that filled it (lamehip_batch_encode) */
 static LhLaunchSerial &
@@ -214,6 +216,22 @@ struct lamehip_batch {
     long    stage_used = 0;     /* shorts staged */
     int     stage_nseg = 0;     /* chunks staged by lamehip_batch_append */
     int     finished = 0;       /* lamehip_batch_finish has run: the streams are closed */
+    /* ... as a pool of B slots (lamehip_batch_end_stream / _restart_stream): a stream ends alone, with the next round -- its
+     * flush planned and encoded as lamehip_batch_finish does it for all of them, its gain and tag frame made --, while the
+     * others go on, and its slot takes the next stream once its bytes have been handed out.  What the restarted slots keep
+     * in HBM from round to round is put back by ONE launch of lh_slot_restart_kernel (lh_slots.hip) on the batch's stream,
+     * at the head of the next round, between ev_sl[0] and ev_sl[1]. */
+    std::vector < char >slot;   /* per stream: LH_SLOT_LIVE, _ENDING (lamehip_batch_end_stream: the next round flushes it), _ENDED */
+    std::vector < char >ending; /* per stream: the round in progress flushes it */
+    std::vector < char >rg_final;       /* per stream: its flush has been analysed, rg_tenths[] is its gain */
+    std::vector < char >tg_has; /* per stream: h_tg_tags holds its final frame */
+    LhPinned < unsigned char >h_tg_round;       /* [B][tg_p.total]: the frames of a round in which only some streams end, on their way */
+    std::vector < int >sl_list, sl_sent;        /* slots restarted since the last round; the list the last restart launch was given */
+    LhDevBuf < int >d_sl_list;
+    LhEvent ev_sl[2];
+    int     sl_ran = 0;         /* the restart launch ev_sl[] are around has not been timed yet */
+    int     sl_gap = 0;         /* sl_ms is a launch of the gap in progress (lamehip_batch_get_state asked for it) */
+    float   sl_ms = 0;
     /* ... on the device packer (lamehip_batch_set_incremental_packing on top of lamehip_batch_set_device_packing): every stream
      * has a fixed slice of the byte pool d_bytes, laid out at the first append from the batch's capacity -- the encode kernel
      * writes at absolute positions across the rounds --, no LhFrameOut comes home and no host packer runs; behind a round's
@@ -302,6 +320,8 @@ struct lamehip_batch {
     std::vector < LhEvent > ev_win;
     int     last_windows = 1;   /* sub-launches of the last launch (1: the whole launch at once) */
 };
+
+enum { LH_SLOT_LIVE = 0, LH_SLOT_ENDING = 1, LH_SLOT_ENDED = 2 };
 
 /* what batch_plan decides about a launch (outside the devices' launch order: it may allocate) and batch_launch carries out */
 struct LhLaunchPlan {
@@ -1091,6 +1111,7 @@ batch_gain_restart(lamehip_batch * b)
     for (std::vector < double >&w:b->rg_win)
         w.clear();
     b->rg_tenths.assign((size_t) b->B, 0);
+    b->rg_final.assign((size_t) b->B, 0);
     b->rg_closed = 0;
     b->rg_measured = 0;
     b->rg_pending = 0;
@@ -1115,6 +1136,7 @@ batch_drain_begin(lamehip_batch * b)
         /* (with tag frames: every stream's carry in front of its first byte and frame, no frame to hand out) */
         HIPCHK(hipMemsetAsync(b->d_tg_carry.get(), 0, (size_t) b->B * sizeof(LhTagCarry), b->stream));
         b->tg_patched.assign((size_t) b->B, 0);
+        b->tg_has.assign((size_t) b->B, 0);
         b->tg_have = 0;
         b->tg_ran = 0;
         b->tag_ms = 0;
@@ -1132,6 +1154,30 @@ batch_drain_begin(lamehip_batch * b)
     return 0;
 }
 
+/* every slot holds a live stream in front of its first sample, and no restart is owed (the records in HBM are put back whole
+ * by whoever calls this) */
+static void
+batch_slots_open(lamehip_batch * b)
+{
+    b->slot.assign((size_t) b->B, (char) LH_SLOT_LIVE);
+    b->ending.assign((size_t) b->B, 0);
+    b->sl_list.clear();
+    b->sl_ran = 0;
+    b->sl_gap = 0;
+    b->sl_ms = 0;
+}
+
+/* stream s takes samples: it has not been ended (lamehip_batch_end_stream), or its slot has been restarted since */
+static int
+batch_slot_takes(const lamehip_batch * b, const char *who, int s)
+{
+    if (b->slot.empty() || b->slot[(size_t) s] == LH_SLOT_LIVE)
+        return 1;
+    snprintf(g_err, sizeof(g_err), "%s: stream %d %s (lamehip_batch_end_stream): lamehip_batch_restart_stream gives its slot to the next "
+             "stream", who, s, b->slot[(size_t) s] == LH_SLOT_ENDING ? "ends with the next round" : "has ended");
+    return 0;
+}
+
 static int
 batch_incremental_begin(lamehip_batch * b, const char *who, int typed_ok)
 {
@@ -1143,6 +1189,7 @@ batch_incremental_begin(lamehip_batch * b, const char *who, int typed_ok)
         return LAMEHIP_ERR_DEVICE;
     if (batch_reset_states(b) != 0 || batch_gain_restart(b) != 0)
         return LAMEHIP_ERR_DEVICE;
+    batch_slots_open(b);
     b->handed.assign((size_t) b->B, std::vector < unsigned char >());
     b->fed.assign((size_t) b->B, 0);
     b->done.assign((size_t) b->B, 0);
@@ -1423,6 +1470,8 @@ lamehip_batch_append(lamehip_batch * b, int s, const short *l, const short *r, i
     }
     if ((rc = batch_incremental_begin(b, "lamehip_batch_append", 0)) != 0)
         return rc;
+    if (!batch_slot_takes(b, "lamehip_batch_append", s))
+        return -1;
     if (n == 0)
         return 0;
     if (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f)
@@ -1516,6 +1565,8 @@ lamehip_batch_append_input(lamehip_batch * b, int s, const void *l, const void *
     }
     if ((rc = batch_append_enter(b, who, stride)) != 0)
         return rc;
+    if (!batch_slot_takes(b, who, s))
+        return -1;
     if (n == 0)
         return 0;
     bool const one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
@@ -1611,6 +1662,8 @@ lamehip_batch_append_input_device(lamehip_batch * b, int s, const void *dl, cons
     }
     if ((rc = batch_append_enter(b, who, stride)) != 0)
         return rc;
+    if (!batch_slot_takes(b, who, s))
+        return -1;
     if (n == 0)
         return 0;
     if (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f)
@@ -1659,6 +1712,9 @@ lamehip_batch_append_device(lamehip_batch * b, const void *dev, long long stream
             snprintf(g_err, sizeof(g_err), "%s: stream %d: a negative length or no samples", who, s);
             return -1;
         }
+        /* (a slot whose stream has been ended takes part in the round with no samples) */
+        if (nsamples[s] > 0 && !batch_slot_takes(b, who, s))
+            return -1;
         if (!batch_append_fits(b, who, s, nsamples[s]))
             return -1;
     }
@@ -1824,14 +1880,16 @@ batch_drain_plan(lamehip_batch * b, const std::vector < int >&upto)
  * bytes are final -- between ev_tg[0] and ev_tg[1].  The final round brings what the kernel cannot know, every stream's end
  * padding: the figure the one-shot tagged path uses for a stream of that many samples, or the conversion's. */
 static int
-batch_tag_launch(lamehip_batch * b, int end)
+batch_tag_launch(lamehip_batch * b, int end, int nending)
 {
     b->tg_ran = 0;
     if (!b->inc_tag || b->tg_p.total <= 0)
         return 0;
-    if (end) {
+    if (nending > 0) {
+        /* (the streams that end in this round: the kernel reads no other's) */
         for (int s = 0; s < b->B; s++)
-            b->h_tg_pad[(size_t) s] = batch_padding(b, s);
+            if (b->ending[(size_t) s])
+                b->h_tg_pad[(size_t) s] = batch_padding(b, s);
         HIPCHK(hipMemcpyAsync(b->d_tg_pad.get(), b->h_tg_pad.data(), (size_t) b->B * sizeof(int), hipMemcpyHostToDevice, b->stream));
     }
     HIPCHK(hipEventRecord(b->ev_tg[0], b->stream));
@@ -1852,6 +1910,12 @@ static int
 batch_drain_launch(lamehip_batch * b, int end)
 {
     LhDrainParams p;
+    int     nending = 0;
+    for (int s = 0; s < b->B; s++)
+        nending += b->ending[(size_t) s] != 0;
+    /* (the kernels take "behind the flush" from every stream's descriptor; the scalar says the same of all streams at once, in
+     * the round that ends them all) */
+    end = end && nending == b->B;
     memset(&p, 0, sizeof(p));
     p.sideinfo_len = b->cfg.sideinfo_len;
     p.frame_factor = (b->cfg.version + 1) * 72000;
@@ -1873,13 +1937,24 @@ batch_drain_launch(lamehip_batch * b, int end)
     HIPCHK(hipEventRecord(b->ev_dr[1], b->stream));
     b->dr_ran = 1;
     {
-        int const tr = batch_tag_launch(b, end);
+        int const tr = batch_tag_launch(b, end, nending);
         if (tr)
             return tr;
     }
     HIPCHK(hipMemcpyAsync(b->h_dr_rows.get(), b->d_dr_rows.get(), ((size_t) b->B + 1) * sizeof(LhDrainRow), hipMemcpyDeviceToHost, b->stream));
-    if (end && b->tg_ran)
-        HIPCHK(hipMemcpyAsync(b->h_tg_tags.get(), b->d_tg_tags.get(), (size_t) b->B * (size_t) b->tg_p.total, hipMemcpyDeviceToHost, b->stream));
+    if (nending > 0 && b->tg_ran) {
+        /* (all streams end: straight to where the getters read; some: the array stops over in a buffer of its own, and the
+         * ending streams' frames alone move on behind the round's wait -- a frame handed out earlier, its gain patched in,
+         * stays as it is) */
+        size_t const room = (size_t) b->B * (size_t) b->tg_p.total;
+        unsigned char *to = b->h_tg_tags.get();
+        if (nending < b->B) {
+            if (!b->h_tg_round.get() && b->h_tg_round.alloc(room) != hipSuccess)
+                return set_err("tag frames: pinned allocation", hipGetLastError());
+            to = b->h_tg_round.get();
+        }
+        HIPCHK(hipMemcpyAsync(to, b->d_tg_tags.get(), room, hipMemcpyDeviceToHost, b->stream));
+    }
     return 0;
 }
 
@@ -1903,8 +1978,21 @@ batch_drain_home(lamehip_batch * b, int end)
             (void) hipGetLastError();
             b->tag_ms = 0;
         }
-        if (end && b->tg_ran)
-            b->tg_have = 1;
+        if (b->tg_ran) {
+            int     nending = 0;
+            for (int s = 0; s < b->B; s++)
+                nending += b->ending[(size_t) s] != 0;
+            for (int s = 0; s < b->B && nending > 0; s++) {
+                if (!b->ending[(size_t) s])
+                    continue;
+                size_t const at = (size_t) s * (size_t) b->tg_p.total;
+                if (nending < b->B)
+                    memcpy(b->h_tg_tags.get() + at, b->h_tg_round.get() + at, (size_t) b->tg_p.total);
+                b->tg_has[(size_t) s] = 1;
+                b->tg_patched[(size_t) s] = 0;
+                b->tg_have = 1;
+            }
+        }
     }
     if (total < 0 || total > b->dr_padded) {
         snprintf(g_err, sizeof(g_err), "incremental packing: the drain found %lld bytes where the round's bound is %lld", total, b->dr_padded);
@@ -1941,14 +2029,92 @@ batch_drain_done(lamehip_batch * b, const std::vector < int >&upto)
     return 0;
 }
 
-/* encode frames [done, upto[s]) of every stream and pack them into pending[]; `end' marks the
- * streams' last frames (flush) */
+/* The slots restarted since the last round: ONE launch of lh_slot_restart_kernel on the batch's stream, between ev_sl[0] and
+ * ev_sl[1], puts their records in HBM back -- in front of everything that reads them: the round's launches, which call this
+ * first, and lamehip_batch_get_state. */
+static int
+batch_restart_launch(lamehip_batch * b)
+{
+    size_t const n = b->sl_list.size();
+    if (n == 0)
+        return 0;
+    if (!b->ev_sl[0] && (b->ev_sl[0].create() != hipSuccess || b->ev_sl[1].create() != hipSuccess))
+        return set_err("hipEventCreate", hipGetLastError());
+    if (!b->d_sl_list.get())
+        HIPCHK(b->d_sl_list.alloc((size_t) b->B));
+    /* (the copy reads the list it is given until the stream has been waited for: the gap's list changes places with the one
+     * of the launch before, which a wait lies behind) */
+    b->sl_sent.swap(b->sl_list);
+    b->sl_list.clear();
+    HIPCHK(hipMemcpyAsync(b->d_sl_list.get(), b->sl_sent.data(), n * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipEventRecord(b->ev_sl[0], b->stream));
+    int const rc = lh_launch_slot_restart(b->d_sl_list.get(), (int) n, b->B, b->d_state.get(), b->d_state0.get(),
+                                          b->inc_pack ? b->d_dr_carry.get() : nullptr, b->inc_tag ? b->d_tg_carry.get() : nullptr,
+                                          b->inc_rg ? b->d_rg_carry.get() : nullptr, (void *) (hipStream_t) b->stream);
+    if (rc)
+        return set_err("slot restart launch", (hipError_t) rc);
+    HIPCHK(hipEventRecord(b->ev_sl[1], b->stream));
+    b->sl_ran = 1;
+    return 0;
+}
+
+/* behind a wait for the batch's stream: the time of the restart launch (lamehip_batch_last_restart_ms) */
+static void
+batch_restart_time(lamehip_batch * b)
+{
+    if (!b->sl_ran)
+        return;
+    b->sl_ran = 0;
+    b->sl_ms = 0;
+    if (hipEventElapsedTime(&b->sl_ms, b->ev_sl[0], b->ev_sl[1]) != hipSuccess) {
+        (void) hipGetLastError();
+        b->sl_ms = 0;
+    }
+}
+
+/* at the head of a round: the gap's restart launch, if one is owed; the figure of lamehip_batch_last_restart_ms is this gap's */
+static int
+batch_restart_round(lamehip_batch * b)
+{
+    if (!b->sl_gap)
+        b->sl_ms = 0;
+    b->sl_gap = 0;
+    return batch_restart_launch(b);
+}
+
+/* behind a round's wait: the streams the round flushed have ended -- on the host packer with the stuffing that completes
+ * their last frame (lh_bs_flush) */
+static void
+batch_round_close(lamehip_batch * b)
+{
+    batch_restart_time(b);
+    for (int s = 0; s < b->B; s++) {
+        if (!b->ending[(size_t) s])
+            continue;
+        if (!b->inc_pack) {
+            LhBitstream *bs = &b->packer[(size_t) s];
+            std::vector < unsigned char >&out = b->pending[(size_t) s];
+            size_t const at = out.size();
+            lh_bs_flush(bs, &b->cfg, b->have_last[(size_t) s] ? &b->last[(size_t) s] : nullptr);
+            out.resize(at + (size_t) lh_bs_pending(bs));
+            int const k = lh_bs_copy(bs, out.data() + at, 0);
+            out.resize(at + (size_t) (k > 0 ? k : 0));
+        }
+        b->ending[(size_t) s] = 0;
+        b->slot[(size_t) s] = (char) LH_SLOT_ENDED;
+    }
+}
+
+/* encode frames [done, upto[s]) of every stream and pack them into pending[]; ending[s] marks the streams whose last frames
+ * these are (flush); `end': the round closes the batch */
 static int
 batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
 {
     LhStreamDesc *descs = (LhStreamDesc *) b->h_stage.get();
     long long total = 0;
     int     rc;
+    if ((rc = batch_restart_round(b)) != 0)
+        return rc;
     /* (a batch that converts: the kernels read the float pool's rows, as far as the conversion has come) */
     long long const row = b->inc_rs ? b->capf : b->cap;
     for (int s = 0; s < b->B; s++) {
@@ -1962,7 +2128,9 @@ batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
         d.out_index = total;
         d.frame_begin = b->done[(size_t) s];
         d.frame_end = upto[(size_t) s];
-        d.flush = end;
+        /* (a stream that ends in this round; a slot whose stream ended in an earlier one keeps the flag, with no frames: the
+         * encode kernels have nothing to do for it, the drain goes on finding its last frame's end) */
+        d.flush = b->ending[(size_t) s] || b->slot[(size_t) s] == LH_SLOT_ENDED;
         if (b->inc_pack) {
             /* (the device packer: the stream's slice, the same in every round) */
             d.bytes_base = b->bytes_off[(size_t) s];
@@ -1993,6 +2161,7 @@ batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
         batch_append_time(b);
         batch_tiles_done(b);
         batch_gain_round_done(b, end);
+        batch_round_close(b);
         return 0;
     }
     {
@@ -2020,6 +2189,7 @@ batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
         for (int s = 0; s < b->B; s++)
             if (upto[(size_t) s] > b->done[(size_t) s])
                 b->done[(size_t) s] = upto[(size_t) s];
+        batch_round_close(b);
         return rc ? rc : (int) total;
     }
     b->h_new.resize((size_t) total);
@@ -2050,15 +2220,74 @@ batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
         if (upto[(size_t) s] > b->done[(size_t) s])
             b->done[(size_t) s] = upto[(size_t) s];
     }
+    batch_round_close(b);
     return (int) total;
+}
+
+static int batch_rs_plan_finish(lamehip_batch * b);
+static int batch_rg_plan_finish(lamehip_batch * b);
+
+/* One round: the frames that became complete of the streams that go on, the flush of those that end with it -- the ones
+ * lamehip_batch_end_stream named, and with `end' (lamehip_batch_finish) every stream that has not ended --, nothing of those
+ * that ended in an earlier round.  who: the entry point, for the messages. */
+static int
+batch_round(lamehip_batch * b, const char *who, int end)
+{
+    std::vector < int >upto;
+    int     rc, nending = 0;
+    if ((rc = batch_incremental_begin(b, who, 0)) != 0)
+        return rc;
+    if ((rc = batch_stage_reserve(b)) != 0)
+        return rc;
+    batch_append_time(b);
+    b->ap_ms = 0;               /* (lamehip_batch_last_append_ms counts from here) */
+    upto.resize((size_t) b->B);
+    for (int s = 0; s < b->B; s++) {
+        b->ending[(size_t) s] = b->slot[(size_t) s] == LH_SLOT_ENDING || (end && b->slot[(size_t) s] == LH_SLOT_LIVE);
+        nending += b->ending[(size_t) s] != 0;
+    }
+    if (end && nending == 0) {
+        /* (every stream has ended on its own: nothing to encode, the batch closes) */
+        b->finished = 1;
+        return 0;
+    }
+    if (nending > 0 && b->inc_rs && (rc = batch_rs_plan_finish(b)) != 0)
+        return rc;
+    if (nending > 0 && b->inc_rg && !b->inc_rs && (rc = batch_rg_plan_finish(b)) != 0)
+        return rc;
+    for (int s = 0; s < b->B; s++) {
+        if (b->slot[(size_t) s] == LH_SLOT_ENDED)
+            upto[(size_t) s] = b->done[(size_t) s];
+        else if (b->ending[(size_t) s]) {
+            if (!b->inc_rs) {
+                long const len = b->fed[(size_t) s] + b->staged[(size_t) s];
+                b->len[(size_t) s] = len;
+                b->nframes[(size_t) s] = lh_total_frames_fs(len, fs_of(b->cfg));
+            }
+            upto[(size_t) s] = b->nframes[(size_t) s];
+        }
+        else
+            upto[(size_t) s] = frames_complete(b->inc_rs ? (long) b->rs_cur[(size_t) s].fed : b->fed[(size_t) s] + b->staged[(size_t) s], b->cfg);
+    }
+    if (b->inc_pack)
+        for (int s = 0; s < b->B; s++)
+            if (b->ending[(size_t) s] && upto[(size_t) s] <= b->done[(size_t) s]) {
+                /* (the kernel's flush -- the stuffing that completes the last frame -- goes with a stream's last frame:
+                 * lh_total_frames_fs leaves every stream at least one for this round, whatever was fed) */
+                snprintf(g_err, sizeof(g_err), "%s: stream %d has no frame left for the flush (%d encoded, %d in all)", who, s,
+                         b->done[(size_t) s], upto[(size_t) s]);
+                return -1;
+            }
+    int const n = batch_encode_range(b, upto, end);
+    if (n >= 0 && end)
+        b->finished = 1;
+    return n;
 }
 
 extern "C" int
 lamehip_batch_encode_available(lamehip_batch * b)
 {
     LhDeviceScope const on_device(b ? b->device : -1);
-    std::vector < int >upto;
-    int     rc;
     if (!b)
         return -1;
     if (b->finished) {
@@ -2067,19 +2296,11 @@ lamehip_batch_encode_available(lamehip_batch * b)
     }
     if (batch_refuse_gain(b, "lamehip_batch_encode_available"))
         return -1;
-    if ((rc = batch_incremental_begin(b, "lamehip_batch_encode_available", 0)) != 0)
-        return rc;
-    if ((rc = batch_stage_reserve(b)) != 0)
-        return rc;
-    batch_append_time(b);
-    b->ap_ms = 0;               /* (lamehip_batch_last_append_ms counts from here) */
-    upto.resize((size_t) b->B);
-    for (int s = 0; s < b->B; s++)
-        upto[(size_t) s] = frames_complete(b->inc_rs ? (long) b->rs_cur[(size_t) s].fed : b->fed[(size_t) s] + b->staged[(size_t) s], b->cfg);
-    return batch_encode_range(b, upto, 0);
+    return batch_round(b, "lamehip_batch_encode_available", 0);
 }
 
-/* A batch that converts round by round, at its end: every stream's flush planned from its cursor (lh_rs_plan_flush) -- its
+/* A batch that converts round by round, at the end of the streams the round ends (ending[]): every such stream's flush
+ * planned from its cursor (lh_rs_plan_flush) -- its
  * tiles join the round's list, its converted length, frame count and end padding are the plan's.  Every append made sure
  * the flush fits the float pool.  An allocation failure returns LAMEHIP_ERR_DEVICE with the batch as it was. */
 static int
@@ -2096,6 +2317,8 @@ batch_rs_plan_finish(lamehip_batch * b)
         for (const std::vector < int >&g:b->rg_blk)
             rg_before.push_back(g.size());
         for (int s = 0; s < b->B; s++) {
+            if (!b->ending[(size_t) s])
+                continue;
             LhRsCursor c = b->rs_cur[(size_t) s];
             int const nblk = lh_rs_plan_flush(b->rs, fs, mfn, &c, nullptr, 0, &padding[(size_t) s]);
             b->rs_blk.resize((size_t) nblk);
@@ -2118,6 +2341,8 @@ batch_rs_plan_finish(lamehip_batch * b)
         return LAMEHIP_ERR_DEVICE;
     }
     for (int s = 0; s < b->B; s++) {
+        if (!b->ending[(size_t) s])
+            continue;
         b->rs_cur[(size_t) s] = end[(size_t) s];
         b->len_in[(size_t) s] = b->fed[(size_t) s] + b->staged[(size_t) s];
         b->len[(size_t) s] = (long) end[(size_t) s].fed;
@@ -2127,7 +2352,8 @@ batch_rs_plan_finish(lamehip_batch * b)
     return 0;
 }
 
-/* A batch that measures ReplayGain round by round and does not convert, at its end: every stream's flush as the analysis
+/* A batch that measures ReplayGain round by round and does not convert, at the end of the streams the round ends (ending[]):
+ * every such stream's flush as the analysis
  * hears it (lh_gain_plan_flush from the stream's cursor) joins the last round's blocks.  Every append made sure it is not too
  * long.  An allocation failure returns LAMEHIP_ERR_DEVICE with the batch as it was. */
 static int
@@ -2136,6 +2362,8 @@ batch_rg_plan_finish(lamehip_batch * b)
     int const fs = fs_of(b->cfg), mfn = mfn_of(b->cfg);
     try {
         for (int s = 0; s < b->B; s++) {
+            if (!b->ending[(size_t) s])
+                continue;
             LhGainCursor c = b->rg_cur[(size_t) s];
             std::vector < int >&g = b->rg_blk[(size_t) s];
             g.reserve(g.size() + (size_t) lh_gain_plan_flush(&c, fs, mfn, nullptr, 0));
@@ -2146,6 +2374,8 @@ batch_rg_plan_finish(lamehip_batch * b)
         return LAMEHIP_ERR_DEVICE;
     }
     for (int s = 0; s < b->B; s++) {
+        if (!b->ending[(size_t) s])
+            continue;
         LhGainCursor c = b->rg_cur[(size_t) s];
         std::vector < int >&g = b->rg_blk[(size_t) s];
         size_t const at = g.size();
@@ -2156,14 +2386,13 @@ batch_rg_plan_finish(lamehip_batch * b)
     return 0;
 }
 
-/* lame_encode_flush for every stream of an incremental batch: the frames still owed for the samples
- * fed (with the reference's end padding), then the stuffing that completes the last frame */
+/* lame_encode_flush for every stream of an incremental batch that has not ended on its own (lamehip_batch_end_stream):
+ * the frames still owed for the samples fed (with the reference's end padding), then the stuffing that completes the last
+ * frame; the streams that have ended stay as they are, and the batch is closed */
 extern "C" int
 lamehip_batch_finish(lamehip_batch * b)
 {
     LhDeviceScope const on_device(b ? b->device : -1);
-    std::vector < int >upto;
-    int     rc, n;
     if (!b)
         return -1;
     if (b->finished) {
@@ -2172,51 +2401,148 @@ lamehip_batch_finish(lamehip_batch * b)
     }
     if (batch_refuse_gain(b, "lamehip_batch_finish"))
         return -1;
-    if ((rc = batch_incremental_begin(b, "lamehip_batch_finish", 0)) != 0)
+    return batch_round(b, "lamehip_batch_finish", 1);
+}
+
+/* ---- the batch as a pool of slots: streams that end and begin on their own ---- */
+
+/* what the two calls check first: 0, or the call's return value */
+static int
+batch_slot_enter(lamehip_batch * b, const char *who, int s)
+{
+    if (!b || s < 0 || s >= b->B) {
+        snprintf(g_err, sizeof(g_err), "%s: no such stream", who);
+        return -1;
+    }
+    if (b->finished) {
+        snprintf(g_err, sizeof(g_err), "%s: the batch is finished (lamehip_batch_reset starts it over)", who);
+        return -1;
+    }
+    return 0;
+}
+
+/* lame_encode_flush for stream s alone, carried out by the next lamehip_batch_encode_available (or lamehip_batch_finish):
+ * nothing is launched here */
+extern "C" int
+lamehip_batch_end_stream(lamehip_batch * b, int s)
+{
+    static const char who[] = "lamehip_batch_end_stream";
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int     rc;
+    if ((rc = batch_slot_enter(b, who, s)) != 0)
         return rc;
-    if ((rc = batch_stage_reserve(b)) != 0)
+    if (batch_refuse_gain(b, who))
+        return -1;
+    if ((rc = batch_incremental_begin(b, who, 0)) != 0)
         return rc;
-    batch_append_time(b);
-    b->ap_ms = 0;
-    upto.resize((size_t) b->B);
+    if (b->slot[(size_t) s] != LH_SLOT_LIVE) {
+        snprintf(g_err, sizeof(g_err), "%s: stream %d %s", who, s,
+                 b->slot[(size_t) s] == LH_SLOT_ENDING ? "ends with the next round already" : "has ended already (lamehip_batch_restart_stream "
+                 "gives its slot to the next stream)");
+        return -1;
+    }
+    b->slot[(size_t) s] = (char) LH_SLOT_ENDING;
+    return 0;
+}
+
+extern "C" int
+lamehip_batch_stream_ended(lamehip_batch * b, int s)
+{
+    if (!b || s < 0 || s >= b->B)
+        return -1;
+    return !b->slot.empty() && b->slot[(size_t) s] == LH_SLOT_ENDED;
+}
+
+/* the slot of stream s, which has ended and whose bytes have been handed out, takes a new stream: the host's books of the
+ * slot in front of the first sample here, its records in HBM with the restart launch at the head of the next round */
+extern "C" int
+lamehip_batch_restart_stream(lamehip_batch * b, int s)
+{
+    static const char who[] = "lamehip_batch_restart_stream";
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int     rc;
+    if ((rc = batch_slot_enter(b, who, s)) != 0)
+        return rc;
+    if (!b->incremental || b->slot[(size_t) s] != LH_SLOT_ENDED) {
+        snprintf(g_err, sizeof(g_err), "%s: stream %d has not ended (lamehip_batch_end_stream, then a round: lamehip_batch_encode_available)",
+                 who, s);
+        return -1;
+    }
+    {
+        long long left = 0;
+        if (!b->inc_pack)
+            left = (long long) b->pending[(size_t) s].size();
+        else if (b->h_dr_rows.get()[s].status == 0)
+            left = b->dr_next[(size_t) s] - b->dr_drained[(size_t) s];
+        if (left > 0) {
+            snprintf(g_err, sizeof(g_err), "%s: stream %d has %lld bytes that have not been handed out (lamehip_batch_drain)", who, s, left);
+            return -1;
+        }
+    }
+    /* everything that can fail first: a failure leaves the slot as it was */
+    {
+        LhBitstream fresh;
+        try {
+            b->sl_list.reserve((size_t) b->B);
+        }
+        catch(const std::bad_alloc &) {
+            snprintf(g_err, sizeof(g_err), "%s: out of memory", who);
+            return LAMEHIP_ERR_DEVICE;
+        }
+        if (lh_bs_init_sized(&fresh, 65536) != 0)
+            return -2;
+        lh_bs_free(&b->packer[(size_t) s]);
+        b->packer[(size_t) s] = fresh;
+    }
+    b->pending[(size_t) s].clear();
+    b->handed[(size_t) s].clear();
+    b->fed[(size_t) s] = 0;
+    b->done[(size_t) s] = 0;
+    b->staged[(size_t) s] = 0;
+    b->have_last[(size_t) s] = 0;
+    b->len[(size_t) s] = 0;
+    b->nframes[(size_t) s] = 0;
+    b->padding[(size_t) s] = 0;
     if (b->inc_rs) {
-        if ((rc = batch_rs_plan_finish(b)) != 0)
-            return rc;
-        for (int s = 0; s < b->B; s++)
-            upto[(size_t) s] = b->nframes[(size_t) s];
+        /* (the converter back in front of the first sample) */
+        lh_rs_cursor_init(&b->rs_cur[(size_t) s]);
+        b->rs_conv[(size_t) s] = 0;
+        b->len_in[(size_t) s] = 0;
     }
-    if (b->inc_rg && !b->inc_rs && (rc = batch_rg_plan_finish(b)) != 0)
-        return rc;
-    for (int s = 0; s < b->B && !b->inc_rs; s++) {
-        long const len = b->fed[(size_t) s] + b->staged[(size_t) s];
-        b->len[(size_t) s] = len;
-        b->nframes[(size_t) s] = lh_total_frames_fs(len, fs_of(b->cfg));
-        upto[(size_t) s] = b->nframes[(size_t) s];
+    if (b->inc_rg) {
+        /* (the analysis likewise: no window, no gain) */
+        lh_gain_cursor_init(&b->rg_cur[(size_t) s]);
+        b->rg_blk[(size_t) s].clear();
+        b->rg_heard[(size_t) s] = 0;
+        b->rg_win[(size_t) s].clear();
+        b->rg_tenths[(size_t) s] = 0;
+        b->rg_final[(size_t) s] = 0;
     }
-    if (b->inc_pack)
-        for (int s = 0; s < b->B; s++)
-            if (upto[(size_t) s] <= b->done[(size_t) s]) {
-                /* (the kernel's flush -- the stuffing that completes the last frame -- goes with a stream's last frame:
-                 * lh_total_frames_fs leaves every stream at least one for this round, whatever was fed) */
-                snprintf(g_err, sizeof(g_err), "lamehip_batch_finish: stream %d has no frame left for the flush (%d encoded, %d in all)", s,
-                         b->done[(size_t) s], upto[(size_t) s]);
-                return -1;
-            }
-    n = batch_encode_range(b, upto, 1);
-    if (n < 0)
-        return n;
-    for (int s = 0; s < b->B && !b->inc_pack; s++) {
-        LhBitstream *bs = &b->packer[(size_t) s];
-        std::vector < unsigned char >&out = b->pending[(size_t) s];
-        size_t  at = out.size();
-        int     k;
-        lh_bs_flush(bs, &b->cfg, b->have_last[(size_t) s] ? &b->last[(size_t) s] : nullptr);
-        out.resize(at + (size_t) lh_bs_pending(bs));
-        k = lh_bs_copy(bs, out.data() + at, 0);
-        out.resize(at + (size_t) (k > 0 ? k : 0));
+    if (b->inc_pack) {
+        /* (nothing handed out, the slice reused from its first byte; the round's table has nothing of the slot any more) */
+        b->dr_drained[(size_t) s] = 0;
+        b->dr_next[(size_t) s] = 0;
+        b->dr_done[(size_t) s] = 0;
+        if (b->h_dr_rows.get()) {
+            b->h_dr_rows.get()[s].n = 0;
+            b->h_dr_rows.get()[s].status = 0;
+        }
     }
-    b->finished = 1;
-    return n;
+    if (b->inc_tag) {
+        b->tg_has[(size_t) s] = 0;
+        b->tg_patched[(size_t) s] = 0;
+    }
+    b->slot[(size_t) s] = (char) LH_SLOT_LIVE;
+    b->sl_list.push_back(s);    /* (room was made above) */
+    return 0;
+}
+
+/* HIP-event time of the restart launch (lh_slot_restart_kernel) in front of the last lamehip_batch_encode_available /
+ * _finish; 0 when no slot was restarted in the gap before it.  Not part of lamehip_batch_last_kernel_ms. */
+extern "C" float
+lamehip_batch_last_restart_ms(lamehip_batch * b)
+{
+    return b ? b->sl_ms : 0.0f;
 }
 
 /* bytes of stream s produced since the last drain; -1 (and nothing taken) when they do not fit */
@@ -2314,6 +2640,8 @@ lamehip_batch_reset(lamehip_batch * b)
         b->ap_nseg = 0;
         b->ap_max_n = 0;
         b->finished = 0;
+        /* (every slot holds a live stream again; what follows puts all records in HBM back, restarted slots' included) */
+        batch_slots_open(b);
         /* (a batch that packs on the device: nothing handed out, the header walks at the slices' first bytes) */
         if (b->inc_pack && batch_drain_begin(b) != 0)
             return LAMEHIP_ERR_DEVICE;
@@ -2670,7 +2998,8 @@ batch_gain_round(lamehip_batch * b)
 }
 
 /* behind the round's wait: the launch's time (lamehip_batch_last_gain_ms), every stream's new windows join its list, the
- * blocks are done with; end: the flush was part of the round, the gains are made of the windows (lh_replaygain.c) */
+ * blocks are done with; the streams the round ends: the flush was part of the round, the gains are made of the windows
+ * (lh_replaygain.c); end: that was the last round of all */
 static void
 batch_gain_round_done(lamehip_batch * b, int end)
 {
@@ -2693,11 +3022,14 @@ batch_gain_round_done(lamehip_batch * b, int end)
         }
         b->h_rg_streams.clear();
     }
-    if (end) {
-        for (int s = 0; s < b->B; s++)
+    /* (the streams the round flushed: their gains are final) */
+    for (int s = 0; s < b->B; s++)
+        if (b->ending[(size_t) s]) {
             b->rg_tenths[(size_t) s] = lh_gain_from_windows(b->rg_win[(size_t) s].data(), (long) (b->rg_win[(size_t) s].size() / 2), W);
+            b->rg_final[(size_t) s] = 1;
+        }
+    if (end)
         b->rg_closed = 1;
-    }
 }
 
 /* the tag of stream s carries its gain when the batch measures it */
@@ -2846,7 +3178,8 @@ batch_gain_ready(lamehip_batch * b, int s, const char *who, bool final = false)
     if (!b || s < 0 || s >= b->B)
         return -1;
     if (b->inc_rg && b->incremental) {
-        if (final && !b->rg_closed) {
+        /* (or after the round that ended the stream alone: lamehip_batch_end_stream) */
+        if (final && !b->rg_final[(size_t) s]) {
             snprintf(g_err, sizeof(g_err), "%s: an incremental batch's gain exists after lamehip_batch_finish (as lame_get_RadioGain's after "
                      "lame_encode_flush)", who);
             return -1;
@@ -3418,18 +3751,30 @@ lamehip_batch_tag_size(lamehip_batch * b)
     return (b && b->inc_tag) ? b->tg_p.total : 0;
 }
 
-/* who: one of the tag getters of an incremental batch */
+/* stream s's tag frame is there: the round that ended it -- lamehip_batch_finish, or the one behind
+ * lamehip_batch_end_stream -- has brought it home (a batch whose tag does not fit a frame has none to bring) */
 static int
-batch_tags_ready(lamehip_batch * b, const char *who)
+batch_tag_there(const lamehip_batch * b, int s)
 {
+    if (!b->incremental || b->slot.empty())
+        return 0;
+    return b->tg_p.total > 0 ? (b->tg_have && b->tg_has[(size_t) s]) : (b->finished || b->slot[(size_t) s] == LH_SLOT_ENDED);
+}
+
+/* who: one of the tag getters of an incremental batch; s: the stream it asks for, or -1: any */
+static int
+batch_tags_ready(lamehip_batch * b, const char *who, int s)
+{
+    int     there = 0;
     if (!b)
         return -1;
     if (!b->inc_tag) {
         snprintf(g_err, sizeof(g_err), "%s: lamehip_batch_set_incremental_tagging is not on", who);
         return -1;
     }
-    /* (a final round has brought them home; a batch whose tag does not fit a frame has none to bring) */
-    if (!(b->tg_p.total > 0 ? b->tg_have : b->finished)) {
+    for (int i = 0; i < b->B && !there; i++)
+        there = (s < 0 || s == i) && batch_tag_there(b, i);
+    if (!there) {
         snprintf(g_err, sizeof(g_err), "%s: an incremental batch's tag frames exist after lamehip_batch_finish", who);
         return -1;
     }
@@ -3450,7 +3795,7 @@ batch_tag_at(lamehip_batch * b, int s, unsigned char **at)
         return LAMEHIP_ERR_PAYLOAD;
     }
     *at = b->h_tg_tags.get() + (size_t) s * (size_t) total;
-    if (b->inc_rg && b->rg_closed && !b->tg_patched[(size_t) s]) {
+    if (b->inc_rg && b->rg_final[(size_t) s] && !b->tg_patched[(size_t) s]) {
         lh_tag_patch_gain(*at, b->tg_p.at, b->rg_tenths[(size_t) s]);
         b->tg_patched[(size_t) s] = 1;
     }
@@ -3463,7 +3808,7 @@ extern "C" long
 lamehip_batch_tag_ptr(lamehip_batch * b, int s, const unsigned char **frame)
 {
     unsigned char *at = nullptr;
-    if (!b || s < 0 || s >= b->B || !frame || batch_tags_ready(b, "lamehip_batch_tag_ptr") != 0)
+    if (!b || s < 0 || s >= b->B || !frame || batch_tags_ready(b, "lamehip_batch_tag_ptr", s) != 0)
         return -1;
     long const n = batch_tag_at(b, s, &at);
     *frame = at;
@@ -3475,10 +3820,15 @@ extern "C" int
 lamehip_batch_get_tags_all(lamehip_batch * b, unsigned char *out, long out_stride, long *sizes)
 {
     int     bad = 0;
-    if (!out || !sizes || batch_tags_ready(b, "lamehip_batch_get_tags_all") != 0)
+    if (!out || !sizes || batch_tags_ready(b, "lamehip_batch_get_tags_all", -1) != 0)
         return -1;
     for (int s = 0; s < b->B; s++) {
         unsigned char *at = nullptr;
+        /* (a stream that has not ended has no frame yet: a negative size, and not an error of the call) */
+        if (!batch_tag_there(b, s)) {
+            sizes[s] = -1;
+            continue;
+        }
         long    n = b->tg_p.total > out_stride ? -1 : batch_tag_at(b, s, &at);
         sizes[s] = n;
         if (n < 0)
@@ -4077,7 +4427,15 @@ lamehip_batch_get_state(lamehip_batch * b, int s, void *out, int size)
     LhDeviceScope const on_device(b ? b->device : -1);
     if (!b || s < 0 || s >= b->B || size < (int) sizeof(LhStreamState))
         return -1;
+    /* (slots restarted since the last round: their records are put back first, and the next round finds nothing owed) */
+    if (!b->sl_list.empty()) {
+        int const rc = batch_restart_launch(b);
+        if (rc)
+            return rc;
+        b->sl_gap = 1;
+    }
     HIPCHK(hipStreamSynchronize(b->stream));
+    batch_restart_time(b);
     HIPCHK(hipMemcpy(out, b->d_state.get() + s, sizeof(LhStreamState), hipMemcpyDeviceToHost));
     return (int) sizeof(LhStreamState);
 }

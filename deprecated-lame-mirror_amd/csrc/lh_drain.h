@@ -24,7 +24,7 @@ typedef struct LhDrainParams {
     int     sideinfo_len;
     int     frame_factor;       /* (version + 1) * 72000: a frame is frame_factor * kbps / samplerate bytes + the padding bit */
     int     samplerate;
-    int     final;              /* behind the flush: P is the end of the last frame */
+    int     final;              /* every stream is behind the flush: P is the end of the last frame (one stream: LhStreamDesc.flush) */
     int16_t kbps[16];           /* the MPEG version's bit rates by index */
 } LhDrainParams;
 

@@ -6,7 +6,8 @@
  *      -- unless the cursor stands one side-information length behind the start of a header that is already out: then the
  *      frame's main data ended on that header exactly, the packer (lh_emit_pos) stepped over it at once, and the reference,
  *      which writes a header only with the next bit behind it, has not written it yet: P is the header's start.  Behind
- *      the flush P is the end of the last frame.  Whether a header starts at cursor - sideinfo_len is found by walking:
+ *      the flush -- of the stream: LhStreamDesc.flush, or of all of them: LhDrainParams.final -- P is the end of the last
+ *      frame.  Whether a header starts at cursor - sideinfo_len is found by walking:
  *      every stream carries the start of a header in HBM (`carry', 0 at first), and the lane moves it on frame by frame --
  *      a frame's length stands in its header's third byte, bit-rate index and padding bit, which the packer has written for
  *      every header in front of em_next_header -- while the next start does not pass the cursor.
@@ -38,13 +39,13 @@
 
 typedef uint32_t lh_dr_v4 __attribute__((vector_size(16)));
 
-/* P of one stream (see above); *carry: the header start the walk has reached */
+/* P of one stream (see above); final: the stream is behind its flush; *carry: the header start the walk has reached */
 LH_DR_FN long long
-drain_position(const LhDrainParams & p, const LhStreamState * st, const unsigned char *slice, long long cap, long long *carry)
+drain_position(const LhDrainParams & p, int final, const LhStreamState * st, const unsigned char *slice, long long cap, long long *carry)
 {
     long long const next = st->em_next_header, cursor = st->em_cursor, target = cursor - p.sideinfo_len;
     long long h = *carry;
-    if (p.final)
+    if (final)
         return next;
     /* (a header at h is in the slice when h lies in front of em_next_header; its frame ends at the next one's start) */
     while (h >= 0 && h < target && h < next && h + 4 <= cap) {
@@ -58,7 +59,10 @@ drain_position(const LhDrainParams & p, const LhStreamState * st, const unsigned
     return (h == target && h < next) ? h : cursor;
 }
 
-/* grid: a lane per stream.  descs: the round's (bytes_base, bytes_cap); drained: what the host has handed out per stream */
+/* grid: a lane per stream.  descs: the round's (bytes_base, bytes_cap, flush); drained: what the host has handed out per
+ * stream.  A stream is behind its flush when the round's descriptor says so -- it ends in this round, or it ended in an
+ * earlier one and its slot has not been restarted: no frames then, and the same P round after round -- or when p.final
+ * says it of all of them. */
 __global__ void
 __launch_bounds__(LH_DR_NT)
 lh_drain_pos_kernel(LhDrainParams p, const LhStreamDesc * descs, const LhStreamState * states, const long long *drained,
@@ -69,7 +73,7 @@ lh_drain_pos_kernel(LhDrainParams p, const LhStreamDesc * descs, const LhStreamS
         return;
     long long const cap = descs[s].bytes_cap, from = drained[s];
     long long h = carry[s];
-    long long const upto = drain_position(p, &states[s], pool + descs[s].bytes_base, cap, &h);
+    long long const upto = drain_position(p, p.final | descs[s].flush, &states[s], pool + descs[s].bytes_base, cap, &h);
     int     status = states[s].status;
     carry[s] = h;
     if (upto < from || upto > cap || from < 0)

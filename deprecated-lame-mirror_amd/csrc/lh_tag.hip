@@ -302,7 +302,10 @@ tag_resume(const LhTagParams & p, const LhTagPow * pw, const unsigned char *slic
 
 /* grid: one workgroup per stream, behind a round's drain.  descs / states: the round's; rows: the drain's table (upto: the
  * position up to which the slice is final); out: the round's records; pool: the byte pool; carry: a record per stream;
- * tags: p.total bytes per stream, written behind the flush only; padding: the end padding per stream, read then */
+ * tags: p.total bytes per stream, written behind the flush only; padding: the end padding per stream, read then.  A stream
+ * is behind its flush in the round in which it ends: its descriptor says flush and names frames (a slot whose stream ended
+ * in an earlier round keeps the flag without frames: its frame has been made and is left alone), or `final' says it of all
+ * streams. */
 __global__ void
 __launch_bounds__(LH_TAG_NT)
 lh_tag_resume_kernel(LhTagParams p, const LhTagPow * pw, const LhStreamDesc * descs, const LhStreamState * states, const LhDrainRow * rows,
@@ -316,7 +319,8 @@ lh_tag_resume_kernel(LhTagParams p, const LhTagPow * pw, const LhStreamDesc * de
     long long const upto = rows[s].upto;
     int const nf = descs[s].frame_end - descs[s].frame_begin;
     int const bad = states[s].status != 0 || rows[s].status != 0 || upto < 0 || upto > descs[s].bytes_cap;
-    tag_resume(p, pw, pool + descs[s].bytes_base, upto, bad, out + descs[s].out_index, nf, final, final ? padding[s] : 0, tmpl, &carry[s],
+    int const ends = final || (descs[s].flush && nf > 0);
+    tag_resume(p, pw, pool + descs[s].bytes_base, upto, bad, out + descs[s].out_index, nf, ends, ends ? padding[s] : 0, tmpl, &carry[s],
                tags + (long long) s * p.total, lds);
 }
 
@@ -447,11 +451,11 @@ lh_emu_tag(const LhTagParams * params, const unsigned char *tmpl, int nstreams, 
  * position the drain found (upto), the status of the packer and of the drain's row, the round's frame count, the end
  * padding, the mode extension of the round's last frame; bitrate_index: the round's lists one behind the other; carry:
  * nstreams records the caller keeps from round to round; tags: nstreams rows of params->total bytes */
-extern "C" int
-lh_emu_tag_resume(const LhTagParams * params, const LhTagPow * pw, const unsigned char *tmpl, int nstreams, const long long *upto,
-                  const int *status, const int *row_status, const int *nframes, const int *padding, const int *last_mode_ext,
-                  const signed char *bitrate_index, const long long *bytes_base, const long long *bytes_cap, const unsigned char *pool,
-                  LhTagCarry * carry, unsigned char *tags, int final)
+static int
+emu_tag_resume(const LhTagParams * params, const LhTagPow * pw, const unsigned char *tmpl, int nstreams, const long long *upto,
+               const int *status, const int *row_status, const int *nframes, const int *padding, const int *last_mode_ext,
+               const signed char *bitrate_index, const long long *bytes_base, const long long *bytes_cap, const unsigned char *pool,
+               LhTagCarry * carry, unsigned char *tags, int final, const int *flush)
 {
     LhTagParams const p = *params;
     std::vector < LhStreamDesc > descs((size_t) (nstreams > 0 ? nstreams : 1));
@@ -471,6 +475,7 @@ lh_emu_tag_resume(const LhTagParams * params, const LhTagPow * pw, const unsigne
         descs[(size_t) s].frame_end = 5 + nframes[s];
         descs[(size_t) s].bytes_base = bytes_base[s];
         descs[(size_t) s].bytes_cap = bytes_cap[s];
+        descs[(size_t) s].flush = flush ? flush[s] : 0;
         states[(size_t) s].status = status[s];
         rows[(size_t) s].status = row_status[s];
         rows[(size_t) s].upto = upto[s];
@@ -492,6 +497,27 @@ lh_emu_tag_resume(const LhTagParams * params, const LhTagPow * pw, const unsigne
                }
     );
     return 0;
+}
+
+extern "C" int
+lh_emu_tag_resume(const LhTagParams * params, const LhTagPow * pw, const unsigned char *tmpl, int nstreams, const long long *upto,
+                  const int *status, const int *row_status, const int *nframes, const int *padding, const int *last_mode_ext,
+                  const signed char *bitrate_index, const long long *bytes_base, const long long *bytes_cap, const unsigned char *pool,
+                  LhTagCarry * carry, unsigned char *tags, int final)
+{
+    return emu_tag_resume(params, pw, tmpl, nstreams, upto, status, row_status, nframes, padding, last_mode_ext, bitrate_index, bytes_base,
+                          bytes_cap, pool, carry, tags, final, nullptr);
+}
+
+/* (tests/hipemu_slots) the same round with the flush per stream, flush[s] = LhStreamDesc.flush of stream s */
+extern "C" int
+lh_emu_tag_resume_slots(const LhTagParams * params, const LhTagPow * pw, const unsigned char *tmpl, int nstreams, const long long *upto,
+                        const int *status, const int *row_status, const int *nframes, const int *padding, const int *last_mode_ext,
+                        const signed char *bitrate_index, const long long *bytes_base, const long long *bytes_cap,
+                        const unsigned char *pool, LhTagCarry * carry, unsigned char *tags, int final, const int *flush)
+{
+    return emu_tag_resume(params, pw, tmpl, nstreams, upto, status, row_status, nframes, padding, last_mode_ext, bitrate_index, bytes_base,
+                          bytes_cap, pool, carry, tags, final, flush);
 }
 
 /* a CRC moved on over n zero bytes through the table, as this library compiled lh_tag.h */

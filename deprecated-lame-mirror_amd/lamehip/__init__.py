@@ -406,6 +406,37 @@ class Batch:
             raise RuntimeError("lamehip_batch_finish failed (%d): %s" % (n, last_error()))
         return n
 
+    def end_stream(self, s):
+        """lame_encode_flush for stream s alone, carried out by the next encode_available() (or finish()) while the other
+        streams go on; launches nothing itself.  From here on appends to s are refused until restart_stream(s)."""
+        self.lib.lamehip_batch_end_stream.argtypes = [C.c_void_p, C.c_int]
+        rc = self.lib.lamehip_batch_end_stream(self.b, s)
+        if rc != 0:
+            raise RuntimeError("lamehip_batch_end_stream failed (%d): %s" % (rc, last_error()))
+
+    def stream_ended(self, s):
+        """True behind the round that ended stream s (end_stream()), until its slot is restarted."""
+        self.lib.lamehip_batch_stream_ended.argtypes = [C.c_void_p, C.c_int]
+        rc = self.lib.lamehip_batch_stream_ended(self.b, s)
+        if rc < 0:
+            raise RuntimeError("lamehip_batch_stream_ended: no stream %d" % s)
+        return bool(rc)
+
+    def restart_stream(self, s):
+        """The slot of stream s, which has ended and been drained, takes a new stream: everything of the old one is gone, the
+        slot's records in HBM are put back by one launch (csrc/lh_slots.hip) at the head of the next round."""
+        self.lib.lamehip_batch_restart_stream.argtypes = [C.c_void_p, C.c_int]
+        rc = self.lib.lamehip_batch_restart_stream(self.b, s)
+        if rc != 0:
+            raise RuntimeError("lamehip_batch_restart_stream failed (%d): %s" % (rc, last_error()))
+
+    def restart_ms(self):
+        """HIP-event time of the restart launch in front of the last encode_available() / finish(); 0 when no slot was
+        restarted in the gap before it."""
+        self.lib.lamehip_batch_last_restart_ms.restype = C.c_float
+        self.lib.lamehip_batch_last_restart_ms.argtypes = [C.c_void_p]
+        return float(self.lib.lamehip_batch_last_restart_ms(self.b))
+
     def drain(self, s, cap=1 << 20):
         """Bytes stream s has produced since its last drain."""
         self.lib.lamehip_batch_drain.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]

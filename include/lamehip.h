@@ -351,7 +351,7 @@ int     lamehip_batch_set_replaygain(lamehip_batch *, int on);
 int     lamehip_batch_set_incremental_replaygain(lamehip_batch *, int on);
 /* stream's radio gain in tenths of a dB (0 when not one 50 ms window was completed); waits for the batch's stream.  -1
  * before a lamehip_batch_encode with the switch on, and again after lamehip_batch_reset; on an incremental batch -1 before
- * lamehip_batch_finish. */
+ * lamehip_batch_finish -- or, for a stream ended on its own, before the round behind its lamehip_batch_end_stream. */
 int     lamehip_batch_radio_gain(lamehip_batch *, int stream, int *tenths_db);
 /* test accessor: what the kernel measured, (left sum, right sum) of the squares of every completed window; writes the first
  * cap_windows pairs and returns the number of windows, or a negative code (an incremental batch: the windows finished so far) */
@@ -371,7 +371,8 @@ float   lamehip_batch_last_gain_ms(lamehip_batch *);
  *   lamehip_batch_drain             the bytes a stream has produced since its last drain: what the
  *                                   reference's lame_encode_buffer returns for the same calls (the output
  *                                   lags the input by the priming: the first 1152 samples yield 0 bytes)
- *   lamehip_batch_finish            lame_encode_flush (lame.h:869, lame.c:2041-2175) for every stream
+ *   lamehip_batch_finish            lame_encode_flush (lame.h:869, lame.c:2041-2175) for every stream that has not
+ *                                   ended on its own (lamehip_batch_end_stream, below); closes the batch
  * The first append switches the batch to this mode (its capacity still bounds a stream's total length).
  * Return codes as lame_encode_buffer's: >= 0, -1 a buffer or the capacity is too small, -2 allocation. */
 int     lamehip_batch_append(lamehip_batch *, int stream, const short *l, const short *r, int nsamples);
@@ -386,7 +387,8 @@ int     lamehip_batch_finish(lamehip_batch *);
  * The first call switches the batch to incremental use whatever its sample type; capacity, lamehip_batch_finish /
  * lamehip_batch_reset and lamehip_batch_drain are as above.  lamehip_batch_append (shorts) stays refused on a batch of
  * another type.  -1, with a lamehip_last_error() that names the call: a stream that would exceed the capacity, a stride
- * other than 1 or 2, a finished batch, a batch that converts the sample rate without
+ * other than 1 or 2, a finished batch, a stream that lamehip_batch_end_stream has ended (until
+ * lamehip_batch_restart_stream; lamehip_batch_append likewise), a batch that converts the sample rate without
  * lamehip_batch_set_incremental_resampling (with it the chunks are at the input rate and go to the input pool as they
  * are, see there), a batch that packs on the device -- refused unless lamehip_batch_set_incremental_packing -- or measures
  * ReplayGain -- refused unless lamehip_batch_set_incremental_replaygain, which has the gain plan follow the calls chunk by
@@ -446,6 +448,46 @@ long    lamehip_batch_drain_ptr(lamehip_batch *, int stream, const unsigned char
 /* HIP-event time in ms of the drain kernels of the last lamehip_batch_encode_available / _finish of a batch with
  * lamehip_batch_set_incremental_packing; 0 when none ran.  Not part of lamehip_batch_last_kernel_ms / _parts_ms. */
 float   lamehip_batch_last_drain_ms(lamehip_batch *);
+/* Streams that come and go: an incremental batch as a pool of slots.  A stream ends alone, with the next round, while the
+ * others go on; its file is complete at once; its slot takes the next stream.  A batch that never makes these calls gets
+ * the launches and the bytes it always got.
+ *   lamehip_batch_end_stream      lame_encode_flush for ONE stream, carried out by the next lamehip_batch_encode_available
+ *                                 (or lamehip_batch_finish): the call launches nothing, a round stays one encode launch for
+ *                                 the whole batch.  It switches a batch that has not been fed to incremental use, as
+ *                                 lamehip_batch_finish does, and is refused where that is (a batch that converts, packs on
+ *                                 the device or measures ReplayGain without its round-by-round switch).  From the call on
+ *                                 appends to the stream are refused: -1, nothing counted, lamehip_last_error() names
+ *                                 lamehip_batch_restart_stream.  The next round encodes the stream's remaining frames with
+ *                                 the reference's end padding and completes its last frame -- on a converting batch behind
+ *                                 the converter's flush, on one that measures ReplayGain with the analysis' flush --, every
+ *                                 other stream's newly complete frames as in any round.  Behind that round
+ *                                 lamehip_batch_stream_ended returns 1, lamehip_batch_drain / _drain_ptr hand over the
+ *                                 stream's last bytes, lamehip_batch_frames is its total, and lamehip_batch_tag_ptr,
+ *                                 lamehip_batch_radio_gain and lamehip_batch_get_gain_windows answer for THAT stream as after
+ *                                 lamehip_batch_finish (for the others the first two stay -1; lamehip_batch_get_tags_all
+ *                                 reports a negative size for them).  An ended stream that is not drained is gathered again
+ *                                 with every round, like any other.  -1, lamehip_last_error() names the call: a finished
+ *                                 batch, a stream that is ending or has ended already, no such stream.
+ *   lamehip_batch_stream_ended    1 behind the round that ended the stream, until its slot is restarted; else 0; -1 for no
+ *                                 such stream
+ *   lamehip_batch_restart_stream  the slot of a stream that HAS ended starts a new one: counters, packer, converter and
+ *                                 analysis back in front of the first sample, windows, gain, tag frame and bytes of the old
+ *                                 stream gone (pointers handed out for it are valid until this call), the slot's slice of the
+ *                                 byte pool reused from its first byte; the slot's capacity bounds the new stream on its
+ *                                 own.  What the slot keeps in HBM -- LhStreamState, the drain's and the tag's carry, the
+ *                                 analysis' -- is put back by ONE launch (csrc/lh_slots.hip: lh_slot_restart_kernel, a
+ *                                 workgroup per restarted slot) at the head of the next round, for all slots restarted since
+ *                                 the last one; no neighbour's record is touched.  -1: the stream has not ended (before its
+ *                                 ending round too), it has bytes that were not handed out (lamehip_last_error() names
+ *                                 lamehip_batch_drain: nothing is lost silently), the batch is finished, no such stream.
+ *   lamehip_batch_last_restart_ms HIP-event time in ms of that launch in front of the last round; 0 when no slot was restarted
+ *                                 in the gap before it.  Not part of lamehip_batch_last_kernel_ms / _parts_ms.
+ * lamehip_batch_finish flushes the streams that have not ended, leaves the others as they are and closes the batch (nothing is
+ * encoded when all have ended); lamehip_batch_reset starts all slots over. */
+int     lamehip_batch_end_stream(lamehip_batch *, int stream);
+int     lamehip_batch_stream_ended(lamehip_batch *, int stream);     /* 1 ended, 0 not, -1 bad argument */
+int     lamehip_batch_restart_stream(lamehip_batch *, int stream);
+float   lamehip_batch_last_restart_ms(lamehip_batch *);
 /* encode every stream completely (all frames incl. the flush frames), payload
  * stays in HBM; asynchronous on the batch's HIP stream */
 int     lamehip_batch_encode(lamehip_batch *);
@@ -526,10 +568,12 @@ float   lamehip_batch_last_tag_ms(lamehip_batch *);
  *   lamehip_batch_tag_size       the frame's length for the batch's settings, constant from the moment the switch is on; 0
  *                                when the tag does not fit a frame (the batch then has no tags, as on the one-shot path) or
  *                                the switch is off
- *   lamehip_batch_tag_ptr        after lamehip_batch_finish: stream's final tag frame in place in the pinned buffer (valid
- *                                until lamehip_batch_reset), returns its length; -1 before lamehip_batch_finish,
- *                                LAMEHIP_ERR_PAYLOAD for a stream whose packer or drain reported a status
- *   lamehip_batch_get_tags_all   frame s at out + s * out_stride, sizes[s] = bytes or a negative code
+ *   lamehip_batch_tag_ptr        after lamehip_batch_finish, or after the round that ended the stream alone
+ *                                (lamehip_batch_end_stream): stream's final tag frame in place in the pinned buffer (valid
+ *                                until lamehip_batch_reset or the slot's lamehip_batch_restart_stream), returns its length;
+ *                                -1 before, LAMEHIP_ERR_PAYLOAD for a stream whose packer or drain reported a status
+ *   lamehip_batch_get_tags_all   frame s at out + s * out_stride, sizes[s] = bytes or a negative code (a stream that has
+ *                                not ended: -1); -1 while no stream has ended
  * The frame is, byte for byte, the one lamehip_batch_pack_tagged / _get_bytes_tagged put in front of the same stream on a
  * one-shot batch fed the same samples.  With lamehip_batch_set_incremental_replaygain on, the radio gain is put into the frame
  * when it is handed out.  lamehip_batch_reset zeroes the carry.  Off (the default): launches, layouts and bytes of every path
@@ -565,7 +609,7 @@ int     lamehip_batch_last_kernel_parts_ms(lamehip_batch *, float *parts3);
 int     lamehip_batch_last_windows(lamehip_batch *);
 /* waves per stream of the kernel this batch encodes with: 2 (one per channel) */
 int     lamehip_batch_kernel_waves(lamehip_batch *);
-int     lamehip_batch_reset(lamehip_batch *);   /* re-initialise all stream states for another run */
+int     lamehip_batch_reset(lamehip_batch *);   /* re-initialise all stream states for another run (an incremental batch: every slot, ended or not) */
 
 /* device self-test of the wave-level primitives the kernels rely on: 0 = pass */
 int     lamehip_selftest(void);
