@@ -23,6 +23,9 @@ extern "C" int lh_launch_append(int type, const LhInParams * p, const LhApSeg * 
 extern "C" int lh_launch_append_raw(int esz, const LhInParams * p, const LhApSeg * segs, int nsegs, long long max_n, void *pool, void *stream);
 extern "C" int lh_launch_resample_tiles(int type, const LhRsParams * p, const float *bank, const LhRsTile * tiles, long long ntiles,
                                         const long long *lens, const void *pcm, float *pcmf, void *stream);
+extern "C" int lh_launch_resample_mixed_tiles(int type, const LhRsParams * p, const LhRsClass * classes, int nclasses, const float *banks,
+                                              const LhRsTile * tiles, long long ntiles, const long long *lens, const void *pcm, float *pcmf,
+                                              void *stream);
 extern "C" int lh_launch_deinterleave(int esz, const void *src_l, const void *src_r, void *dst_l, void *dst_r, long long n, void *stream);
 extern "C" int lh_launch_gain(int floats, const LhGainParams * p, const LhGainStream * streams, int nstreams, const int *trunk, const int *tails,
                               const void *pool, double *pairs, void *stream);
@@ -164,6 +167,18 @@ struct lamehip_batch {
     std::vector < long long >h_rs_lens; /* input samples per stream, as the round's launch sees them */
     LhDevBuf < LhRsTile > d_tiles;
     LhDevBuf < long long >d_rs_lens;
+    /* ... with streams at input rates of their own (lamehip_batch_set_stream_in_samplerate): every distinct rate is a CLASS
+     * -- a converter for the plans, made on first use and kept until the batch goes; class 0 is the batch's own rate, `rs' --,
+     * a stream's appends and flush are planned with its class's converter and its tiles carry the class, and a round in which
+     * a stream has a class other than 0 is converted by ONE launch of lh_resample_mixed_tiles_kernel, which reads the class
+     * table and all banks from HBM.  Nothing of this exists in a batch that never makes the call. */
+    LhUserParams user_p;        /* the handle's settings: a new rate is accepted when they resolve to this batch's records with it */
+    int     rs_ncls = 0;        /* classes made (0: the call was never accepted for another rate than the batch's) */
+    LhResampler *rs_cls[LH_RS_CLASSES_MAX] = { };       /* [0] is `rs'; the others are the batch's to free */
+    LhRsClass h_rs_cls[LH_RS_CLASSES_MAX] = { };
+    std::vector < int >rs_scls; /* per stream: its class (empty until the first class is made) */
+    LhDevBuf < float >d_rs_banks;       /* LH_RS_CLASSES_MAX banks of 2 * LH_RS_MAXPHASES + 1 rows of LH_RS_ROW floats */
+    LhDevBuf < LhRsClass > d_rs_classes;
     /* ReplayGain (lamehip_batch_set_replaygain): lamehip_batch_encode measures the radio gain of the streams declared since
      * their last analysis with lh_gain.hip, behind the conversion / ingest kernels and in front of the analysis kernels.  The
      * host plans (lh_gain_plan: the blocks the handle API would hand to lh_rg_block), the kernel leaves every stream's window
@@ -534,6 +549,41 @@ batch_reads_floats(const lamehip_batch * b)
     return b->rate_in || b->stype != LH_PCM_S16;
 }
 
+/* the rate class of stream s, and the converter its calls are planned with */
+static int
+batch_stream_cls(const lamehip_batch * b, int s)
+{
+    return b->rs_scls.empty() ? 0 : b->rs_scls[(size_t) s];
+}
+
+static const LhResampler *
+batch_stream_rs(const lamehip_batch * b, int s)
+{
+    return b->rs_scls.empty() ? b->rs : b->rs_cls[b->rs_scls[(size_t) s]];
+}
+
+/* a stream has an input rate other than the batch's (lamehip_batch_set_stream_in_samplerate) */
+static int
+batch_own_rates(const lamehip_batch * b)
+{
+    for (int c:b->rs_scls)
+        if (c != 0)
+            return 1;
+    return 0;
+}
+
+/* what the whole-stream calls say to a batch with such a stream: the one-shot converter shares one trunk of blocks between
+ * all streams and stays single-rate.  Returns 0 when there is none */
+static int
+batch_refuse_own_rates(const lamehip_batch * b, const char *who)
+{
+    if (!b || !batch_own_rates(b))
+        return 0;
+    snprintf(g_err, sizeof(g_err), "%s: a stream of this batch has an input rate of its own (lamehip_batch_set_stream_in_samplerate): "
+             "such a batch is fed with appends, the one-shot converter is single-rate", who);
+    return -1;
+}
+
 /* row ch of stream s in the input pool / in its pinned mirror */
 static unsigned char *
 batch_pool_row(const lamehip_batch * b, int s, int ch)
@@ -602,6 +652,7 @@ lamehip_batch_create_on(int device, const lame_t proto, int nstreams, long capac
         return nullptr;
     b->device = device;
     b->cfg = proto->cfg;
+    b->user_p = proto->p;
     b->tab = (LhTables *) malloc(sizeof(LhTables));
     if (!b->tab) {
         delete  b;
@@ -656,6 +707,8 @@ lamehip_batch_destroy(lamehip_batch * b)
     for (size_t i = 0; i < b->packer.size(); i++)
         lh_bs_free(&b->packer[i]);
     lh_rs_trunk_free(&b->trunk);
+    for (int c = 1; c < b->rs_ncls; c++)
+        free(b->rs_cls[c]);
     free(b->rs);
     free(b->tab);
     b->dc.release();
@@ -718,6 +771,8 @@ lamehip_batch_set_length(lamehip_batch * b, int s, long n)
 {
     if (!b || s < 0 || s >= b->B || n < 0 || (b->rate_in && !b->dev_rs))
         return -1;              /* (a batch that converts on the host needs the samples themselves: lamehip_batch_set_pcm) */
+    if (batch_refuse_own_rates(b, "lamehip_batch_set_length"))
+        return -1;
     if (n > b->cap) {
         snprintf(g_err, sizeof(g_err), "lamehip_batch_set_length: stream of %ld samples exceeds the pool (%ld per stream)", n, b->cap);
         return -1;
@@ -803,6 +858,8 @@ extern "C" int
 lamehip_batch_set_pcm(lamehip_batch * b, int s, const short *l, const short *r, long n)
 {
     LhDeviceScope const on_device(b ? b->device : -1);
+    if (batch_refuse_own_rates(b, "lamehip_batch_set_pcm"))
+        return -1;
     if (b && b->stype != LH_PCM_S16) {
         snprintf(g_err, sizeof(g_err), "lamehip_batch_set_pcm: this batch's sample type is not s16 (lamehip_batch_set_input takes its samples)");
         return -1;
@@ -950,6 +1007,8 @@ lamehip_batch_set_input(lamehip_batch * b, int s, const void *l, const void *r, 
         snprintf(g_err, sizeof(g_err), "lamehip_batch_set_input: no such stream, a negative length or a stride other than 1 or 2");
         return -1;
     }
+    if (batch_refuse_own_rates(b, "lamehip_batch_set_input"))
+        return -1;
     bool const one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
     if (one_plane)
         r = l;                  /* mono: the second plane mirrors the first, the kernel never uses it */
@@ -1000,6 +1059,8 @@ lamehip_batch_set_input_device(lamehip_batch * b, int s, const void *dl, const v
         snprintf(g_err, sizeof(g_err), "lamehip_batch_set_input_device: stride %d (1: planar, 2: interleaved)", stride);
         return -1;
     }
+    if (batch_refuse_own_rates(b, "lamehip_batch_set_input_device"))
+        return -1;
     if (lamehip_batch_set_length(b, s, n) != 0)
         return -1;
     bool const one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
@@ -1039,6 +1100,8 @@ lamehip_batch_set_pcm_device(lamehip_batch * b, int s, const void *dl, const voi
         snprintf(g_err, sizeof(g_err), "lamehip_batch_set_pcm_device: this batch's sample type is not s16 (lamehip_batch_set_input_device)");
         return -1;
     }
+    if (batch_refuse_own_rates(b, "lamehip_batch_set_pcm_device"))
+        return -1;
     if (lamehip_batch_set_length(b, s, n) != 0)
         return -1;
     if (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f)
@@ -1355,10 +1418,12 @@ static int
 batch_rs_plan_append(lamehip_batch * b, const char *who, int s, int n, bool commit, size_t *ntiles = nullptr)
 {
     int const fs = fs_of(b->cfg), mfn = mfn_of(b->cfg);
+    const LhResampler *const rs = batch_stream_rs(b, s);        /* (the stream's own converter) */
+    int const cls = batch_stream_cls(b, s);
     LhRsCursor c = b->rs_cur[(size_t) s], end;
     int     padding = 0;
     size_t  nt = 0;
-    int const nblk = lh_rs_plan_call(b->rs, fs, mfn, &c, n, nullptr, 0);
+    int const nblk = lh_rs_plan_call(rs, fs, mfn, &c, n, nullptr, 0);
     try {
         b->rs_blk.resize((size_t) nblk);
     }
@@ -1367,9 +1432,9 @@ batch_rs_plan_append(lamehip_batch * b, const char *who, int s, int n, bool comm
         return LAMEHIP_ERR_DEVICE;
     }
     c = b->rs_cur[(size_t) s];
-    (void) lh_rs_plan_call(b->rs, fs, mfn, &c, n, b->rs_blk.data(), nblk);
+    (void) lh_rs_plan_call(rs, fs, mfn, &c, n, b->rs_blk.data(), nblk);
     end = c;
-    (void) lh_rs_plan_flush(b->rs, fs, mfn, &end, nullptr, 0, &padding);
+    (void) lh_rs_plan_flush(rs, fs, mfn, &end, nullptr, 0, &padding);
     if (end.fed > (long long) b->inc_capf) {
         snprintf(g_err, sizeof(g_err), "%s: stream %d, flushed behind this call, would be %lld converted samples: more than the float pool's "
                  "%ld per stream", who, s, end.fed, b->inc_capf);
@@ -1391,7 +1456,7 @@ batch_rs_plan_append(lamehip_batch * b, const char *who, int s, int n, bool comm
         }
     }
     for (const LhRsBlock & k:b->rs_blk)
-        nt += (size_t) lh_rs_block_tiles(b->rs, &k, s, nullptr, 0);
+        nt += (size_t) lh_rs_block_tiles_class(rs, &k, s, cls, nullptr, 0);
     if (ntiles)
         *ntiles += nt;
     if (!commit)
@@ -1406,7 +1471,7 @@ batch_rs_plan_append(lamehip_batch * b, const char *who, int s, int n, bool comm
     }
     nt = at;
     for (const LhRsBlock & k:b->rs_blk)
-        nt += (size_t) lh_rs_block_tiles(b->rs, &k, s, b->h_tiles.data() + nt, (int) (b->h_tiles.size() - nt));
+        nt += (size_t) lh_rs_block_tiles_class(rs, &k, s, cls, b->h_tiles.data() + nt, (int) (b->h_tiles.size() - nt));
     if (b->inc_rg)
         for (const LhRsBlock & k:b->rs_blk)
             if (k.made > 0)
@@ -1803,9 +1868,21 @@ batch_tiles_launch(lamehip_batch * b)
     p.one_plane = (b->cfg.channels == 1 && b->cfg.pcm_mix == 0.0f);
     p.cap_in = b->cap;
     p.cap_out = b->capf;
+    /* (a round with a tile of another class than the batch's own: the mixed kernel) */
+    bool    mixed = false;
+    if (b->rs_ncls > 1)
+        for (const LhRsTile & t:b->h_tiles)
+            if (t.cls != 0) {
+                mixed = true;
+                break;
+            }
     HIPCHK(hipEventRecord(b->ev_rs[0], b->stream));
-    int const rc = lh_launch_resample_tiles(b->stype, &p, b->d_rs_bank.get(), b->d_tiles.get(), (long long) ntiles, b->d_rs_lens.get(),
-                                            b->d_pcm.get(), b->d_pcmf.get(), (void *) (hipStream_t) b->stream);
+    int const rc = mixed
+        ? lh_launch_resample_mixed_tiles(b->stype, &p, b->d_rs_classes.get(), b->rs_ncls, b->d_rs_banks.get(), b->d_tiles.get(),
+                                         (long long) ntiles, b->d_rs_lens.get(), b->d_pcm.get(), b->d_pcmf.get(),
+                                         (void *) (hipStream_t) b->stream)
+        : lh_launch_resample_tiles(b->stype, &p, b->d_rs_bank.get(), b->d_tiles.get(), (long long) ntiles, b->d_rs_lens.get(),
+                                   b->d_pcm.get(), b->d_pcmf.get(), (void *) (hipStream_t) b->stream);
     if (rc)
         return set_err("conversion launch", (hipError_t) rc);
     HIPCHK(hipEventRecord(b->ev_rs[1], b->stream));
@@ -1876,9 +1953,25 @@ batch_drain_plan(lamehip_batch * b, const std::vector < int >&upto)
     return 0;
 }
 
+/* the info byte of the LAME extension for a stream that arrives at rate_in: lh_tag_template's, made as the batch's own
+ * template is (lamehip_batch_set_incremental_tagging) with that source rate */
+static int
+batch_tag_info(const lamehip_batch * b, int rate_in)
+{
+    unsigned char frame[2880]; /* (lh_tag_init allows no larger frame) */
+    LhVbrTag v;
+    int const total = lh_tag_init(&v, &b->cfg);
+    if (total <= 0 || total > (int) sizeof(frame))
+        return 0;
+    v.samplerate_in = rate_in;
+    lh_tag_template(&v, &b->cfg, b->cfg.vbr_q, frame);
+    return frame[b->tg_p.at + LH_TAG_AT_EXT + LH_TAG_EXT_INFO];
+}
+
 /* A round's tag launch (lamehip_batch_set_incremental_tagging), behind the drain's launches -- its table in HBM says which
  * bytes are final -- between ev_tg[0] and ev_tg[1].  The final round brings what the kernel cannot know, every stream's end
- * padding: the figure the one-shot tagged path uses for a stream of that many samples, or the conversion's. */
+ * padding: the figure the one-shot tagged path uses for a stream of that many samples, or the conversion's -- and with it
+ * the info byte of a stream at an input rate of its own (lh_tag.h: lh_tag_pad_with_info). */
 static int
 batch_tag_launch(lamehip_batch * b, int end, int nending)
 {
@@ -1888,8 +1981,12 @@ batch_tag_launch(lamehip_batch * b, int end, int nending)
     if (nending > 0) {
         /* (the streams that end in this round: the kernel reads no other's) */
         for (int s = 0; s < b->B; s++)
-            if (b->ending[(size_t) s])
+            if (b->ending[(size_t) s]) {
                 b->h_tg_pad[(size_t) s] = batch_padding(b, s);
+                /* (a stream at an input rate of its own: its info byte, which the template has for the batch's rate) */
+                if (batch_stream_cls(b, s) != 0)
+                    b->h_tg_pad[(size_t) s] = lh_tag_pad_with_info(b->h_tg_pad[(size_t) s], batch_tag_info(b, batch_stream_rs(b, s)->rate_in));
+            }
         HIPCHK(hipMemcpyAsync(b->d_tg_pad.get(), b->h_tg_pad.data(), (size_t) b->B * sizeof(int), hipMemcpyHostToDevice, b->stream));
     }
     HIPCHK(hipEventRecord(b->ev_tg[0], b->stream));
@@ -2319,17 +2416,19 @@ batch_rs_plan_finish(lamehip_batch * b)
         for (int s = 0; s < b->B; s++) {
             if (!b->ending[(size_t) s])
                 continue;
+            const LhResampler *const rs = batch_stream_rs(b, s);
+            int const cls = batch_stream_cls(b, s);
             LhRsCursor c = b->rs_cur[(size_t) s];
-            int const nblk = lh_rs_plan_flush(b->rs, fs, mfn, &c, nullptr, 0, &padding[(size_t) s]);
+            int const nblk = lh_rs_plan_flush(rs, fs, mfn, &c, nullptr, 0, &padding[(size_t) s]);
             b->rs_blk.resize((size_t) nblk);
-            (void) lh_rs_plan_flush(b->rs, fs, mfn, &end[(size_t) s], b->rs_blk.data(), nblk, &padding[(size_t) s]);
+            (void) lh_rs_plan_flush(rs, fs, mfn, &end[(size_t) s], b->rs_blk.data(), nblk, &padding[(size_t) s]);
             for (const LhRsBlock & k:b->rs_blk)
                 if (b->inc_rg && k.made > 0)
                     b->rg_blk[(size_t) s].push_back(k.made);
             for (const LhRsBlock & k:b->rs_blk) {
                 size_t const at = b->h_tiles.size();
-                b->h_tiles.resize(at + (size_t) lh_rs_block_tiles(b->rs, &k, s, nullptr, 0));
-                (void) lh_rs_block_tiles(b->rs, &k, s, b->h_tiles.data() + at, (int) (b->h_tiles.size() - at));
+                b->h_tiles.resize(at + (size_t) lh_rs_block_tiles_class(rs, &k, s, cls, nullptr, 0));
+                (void) lh_rs_block_tiles_class(rs, &k, s, cls, b->h_tiles.data() + at, (int) (b->h_tiles.size() - at));
             }
         }
     }
@@ -2508,6 +2607,9 @@ lamehip_batch_restart_stream(lamehip_batch * b, int s)
         lh_rs_cursor_init(&b->rs_cur[(size_t) s]);
         b->rs_conv[(size_t) s] = 0;
         b->len_in[(size_t) s] = 0;
+        /* (... and at the batch's own rate: the slot's next tenant states its rate again) */
+        if (!b->rs_scls.empty())
+            b->rs_scls[(size_t) s] = 0;
     }
     if (b->inc_rg) {
         /* (the analysis likewise: no window, no gain) */
@@ -2654,6 +2756,8 @@ lamehip_batch_reset(lamehip_batch * b)
         if (batch_gain_restart(b) != 0)
             return LAMEHIP_ERR_DEVICE;
     }
+    /* (every stream back at the batch's own input rate; the classes made stay) */
+    b->rs_scls.assign(b->rs_scls.size(), 0);
     /* every gain is forgotten, and every stream with it: the next encode measures all of them again */
     b->rg_measured = 0;
     b->rg_pending = 0;
@@ -3270,6 +3374,8 @@ lamehip_batch_encode(lamehip_batch * b)
     LhDeviceScope const on_device(b ? b->device : -1);
     long long total = 0, bytes_total = 0;
     if (!b)
+        return -1;
+    if (batch_refuse_own_rates(b, "lamehip_batch_encode"))
         return -1;
     if (b->incremental) {
         snprintf(g_err, sizeof(g_err), "lamehip_batch_encode: this batch is fed with lamehip_batch_append (incremental use)");
@@ -4052,6 +4158,199 @@ lamehip_batch_set_incremental_resampling(lamehip_batch * b, int on)
     }
     b->inc_rs = 1;
     return 0;
+}
+
+/* ---- streams at input rates of their own (lamehip_batch_set_stream_in_samplerate) ---- */
+
+/* A rate is accepted when the library's own host init resolves this batch's records again for it: the handle's settings with
+ * in = hz and the batch's output rate given explicitly.  The records are compared whole -- the input rate is in neither of
+ * them --; nothing here reasons about which setting might matter.  0, -1 with a message that names what differs, or
+ * LAMEHIP_ERR_DEVICE. */
+static int
+batch_rate_resolves(const lamehip_batch * b, const char *who, int hz)
+{
+    LhUserParams p = b->user_p;
+    LhConfig cfg;
+    LhInitAux aux;
+    int     rc = 0;
+    LhTables *tab = (LhTables *) malloc(sizeof(LhTables));
+    if (!tab) {
+        snprintf(g_err, sizeof(g_err), "%s: out of memory (tables)", who);
+        return LAMEHIP_ERR_DEVICE;
+    }
+    p.samplerate = hz;
+    p.samplerate_out = b->cfg.samplerate;
+    if (lh_config_resolve(&p, &cfg, &aux) != 0 || lh_tables_build(&cfg, &aux, tab) != 0) {
+        snprintf(g_err, sizeof(g_err), "%s: the batch's settings do not resolve for %d Hz in, %d Hz out", who, hz, b->cfg.samplerate);
+        rc = -1;
+    }
+    else {
+        const unsigned char *x = (const unsigned char *) &cfg, *y = (const unsigned char *) &b->cfg;
+        size_t  at;
+        for (at = 0; at < sizeof(LhConfig) && x[at] == y[at]; at++);
+        if (at < sizeof(LhConfig)) {
+            snprintf(g_err, sizeof(g_err), "%s: at %d Hz in (%d Hz out) the settings resolve to another LhConfig than the batch's: byte %zu "
+                     "differs", who, hz, b->cfg.samplerate, at);
+            rc = -1;
+        }
+        x = (const unsigned char *) tab;
+        y = (const unsigned char *) b->tab;
+        for (at = 0; rc == 0 && at < sizeof(LhTables) && x[at] == y[at]; at++);
+        if (rc == 0 && at < sizeof(LhTables)) {
+            snprintf(g_err, sizeof(g_err), "%s: at %d Hz in (%d Hz out) the settings resolve to other LhTables than the batch's: byte %zu "
+                     "differs", who, hz, b->cfg.samplerate, at);
+            rc = -1;
+        }
+    }
+    free(tab);
+    return rc;
+}
+
+/* The class of input rate hz, made on first use: its converter for the plans, its bank in HBM, its record in the class table.
+ * The first class made brings the table and the room for all banks (one allocation, class 0's bank copied into it).
+ * Everything is allocated first: a failure returns LAMEHIP_ERR_DEVICE and leaves the batch as it was; -1: refused. */
+static int
+batch_rate_class(lamehip_batch * b, const char *who, int hz, int *cls)
+{
+    size_t const bank_floats = (size_t) (2 * LH_RS_MAXPHASES + 1) * LH_RS_ROW;
+    int const ncls = b->rs_ncls ? b->rs_ncls : 1;
+    bool const first = b->rs_ncls == 0;
+    int     rc;
+    *cls = 0;
+    if (hz == b->rate_in)
+        return 0;
+    for (int c = 1; c < b->rs_ncls; c++)
+        if (b->rs_cls[c]->rate_in == hz) {
+            *cls = c;
+            return 0;
+        }
+    if (ncls >= LH_RS_CLASSES_MAX) {
+        snprintf(g_err, sizeof(g_err), "%s: this batch has had %d distinct input rates already (LH_RS_CLASSES_MAX), %d Hz would be one more",
+                 who, ncls, hz);
+        return -1;
+    }
+    if ((rc = batch_rate_resolves(b, who, hz)) != 0)
+        return rc;
+    LhResampler *r = (LhResampler *) malloc(sizeof(LhResampler));
+    LhDevBuf < float >banks;
+    LhDevBuf < LhRsClass > classes;
+    std::vector < int >scls;
+    std::vector < float >h_bank;
+    LhRsClass rec[2];
+    hipError_t e = r ? hipSuccess : hipErrorOutOfMemory;
+    memset(rec, 0, sizeof(rec));
+    try {
+        if (first)
+            scls.assign((size_t) b->B, 0);
+        h_bank.assign(bank_floats, 0.0f);
+    }
+    catch(const std::bad_alloc &) {
+        e = hipErrorOutOfMemory;
+    }
+    if (e == hipSuccess) {
+        if (lh_rs_needed(hz, b->cfg.samplerate)) {
+            lh_rs_init(r, hz, b->cfg.samplerate);
+            for (int k = 0; k < 2 * r->phases + 1; k++)
+                memcpy(&h_bank[(size_t) k * LH_RS_ROW], r->bank[k], (size_t) (r->taps + 1) * sizeof(float));
+        }
+        else
+            lh_rs_init_identity(r, hz, b->cfg.samplerate);
+        rec[1].ratio = r->ratio;
+        rec[1].taps = r->taps;
+        rec[1].phases = r->phases;
+        rec[1].identity = lh_rs_is_identity(r);
+        rec[1].bank_at = (long long) ((size_t) ncls * bank_floats);
+        rec[0].ratio = b->rs->ratio;
+        rec[0].taps = b->rs->taps;
+        rec[0].phases = b->rs->phases;
+    }
+    if (e == hipSuccess && first)
+        e = banks.alloc((size_t) LH_RS_CLASSES_MAX * bank_floats);
+    if (e == hipSuccess && first)
+        e = classes.alloc(LH_RS_CLASSES_MAX);
+    float  *const d_banks = first ? banks.get() : b->d_rs_banks.get();
+    LhRsClass *const d_classes = first ? classes.get() : b->d_rs_classes.get();
+    if (e == hipSuccess && first)
+        e = hipMemset(d_banks, 0, (size_t) LH_RS_CLASSES_MAX * bank_floats * sizeof(float));
+    if (e == hipSuccess && first)
+        e = hipMemset(d_classes, 0, LH_RS_CLASSES_MAX * sizeof(LhRsClass));
+    if (e == hipSuccess && first)
+        e = hipMemcpy(d_banks, b->d_rs_bank.get(), (size_t) (2 * b->rs->phases + 1) * LH_RS_ROW * sizeof(float), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && first)
+        e = hipMemcpy(d_classes, &rec[0], sizeof(LhRsClass), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !rec[1].identity)
+        e = hipMemcpy(d_banks + (size_t) ncls * bank_floats, h_bank.data(), bank_floats * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(d_classes + ncls, &rec[1], sizeof(LhRsClass), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        free(r);
+        return set_err("lamehip_batch_set_stream_in_samplerate: allocation", e);
+    }
+    if (first) {
+        b->d_rs_banks = std::move(banks);
+        b->d_rs_classes = std::move(classes);
+        b->rs_scls = std::move(scls);
+        b->rs_cls[0] = b->rs;
+        b->h_rs_cls[0] = rec[0];
+    }
+    b->rs_cls[ncls] = r;
+    b->h_rs_cls[ncls] = rec[1];
+    b->rs_ncls = ncls + 1;
+    *cls = ncls;
+    return 0;
+}
+
+/* Stream s arrives at hz (include/lamehip.h has the contract): from here on its appends and its flush are planned with the
+ * converter of that rate's class -- or not converted at all, where the reference would not --, and its tag frame names the
+ * rate.  For a batch that converts round by round, and a stream that has nothing appended yet. */
+extern "C" int
+lamehip_batch_set_stream_in_samplerate(lamehip_batch * b, int s, int hz)
+{
+    static const char who[] = "lamehip_batch_set_stream_in_samplerate";
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int     rc, cls = 0;
+    if (!b || s < 0 || s >= b->B) {
+        snprintf(g_err, sizeof(g_err), "%s: no such stream", who);
+        return -1;
+    }
+    if (hz <= 0) {
+        snprintf(g_err, sizeof(g_err), "%s: an input rate of %d Hz", who, hz);
+        return -1;
+    }
+    if (!b->inc_rs) {
+        snprintf(g_err, sizeof(g_err), "%s: for a batch that converts the sample rate round by round (lamehip_batch_set_device_resampling, "
+                 "then lamehip_batch_set_incremental_resampling)", who);
+        return -1;
+    }
+    if (b->finished) {
+        snprintf(g_err, sizeof(g_err), "%s: the batch is finished (lamehip_batch_reset starts it over)", who);
+        return -1;
+    }
+    if (b->incremental
+        && (b->slot[(size_t) s] != LH_SLOT_LIVE || b->fed[(size_t) s] + b->staged[(size_t) s] > 0 || b->rs_cur[(size_t) s].in_at > 0)) {
+        snprintf(g_err, sizeof(g_err), "%s: stream %d %s: a stream's rate is stated before its first sample (in a fresh batch, after "
+                 "lamehip_batch_reset or lamehip_batch_restart_stream)", who, s,
+                 b->slot[(size_t) s] != LH_SLOT_LIVE ? "has ended" : "has samples already");
+        return -1;
+    }
+    if ((rc = batch_rate_class(b, who, hz, &cls)) != 0)
+        return rc;
+    if (!b->rs_scls.empty())
+        b->rs_scls[(size_t) s] = cls;
+    return 0;
+}
+
+/* the input rate of stream s: the batch's own when none was stated; -1: no such stream */
+extern "C" int
+lamehip_batch_stream_in_samplerate(lamehip_batch * b, int s)
+{
+    if (!b || s < 0 || s >= b->B) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_stream_in_samplerate: no such stream");
+        return -1;
+    }
+    int const cls = batch_stream_cls(b, s);
+    return cls ? b->rs_cls[cls]->rate_in : b->rate_in ? b->rate_in : b->cfg.samplerate;
 }
 
 /* The sample type of the input pool (LAMEHIP_PCM_*), only before any PCM is handed over.  Other than s16 the batch gets an

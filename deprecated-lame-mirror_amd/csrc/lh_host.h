@@ -220,6 +220,13 @@ int     lh_rs_plan_flush(const LhResampler * r, int fs, int mfn, LhRsCursor * c,
 /* the tiles of one block, in output order: each as many outputs as touch at most LH_RS_SPAN_MAX input positions, measured
  * with lh_rs_locate; none for a block that makes nothing.  Returns their number, only the first `cap' are written */
 int     lh_rs_block_tiles(const LhResampler * r, const LhRsBlock * b, int stream, LhRsTile * tiles, int cap);
+/* ... with the tiles' rate class written into them (lh_rs_block_tiles: class 0) */
+int     lh_rs_block_tiles_class(const LhResampler * r, const LhRsBlock * b, int stream, int cls, LhRsTile * tiles, int cap);
+/* The pass-through plan: a stream whose rate the reference does not convert (lh_rs_needed == 0) gets a converter without
+ * a bank, with which lh_rs_plan_call / _flush cut the blocks fill_buffer cuts -- made = used = min(frame size, samples
+ * at hand) -- and the flush owes nothing for a converter's delay; lh_rs_block_tiles gives every such block one tile. */
+void    lh_rs_init_identity(LhResampler * r, int rate_in, int rate_out);
+int     lh_rs_is_identity(const LhResampler * r);
 /* one block of a plan evaluated on the host, sample by sample as the device kernel does it: writes
  * out_l / out_r [out_at, out_at + made) */
 void    lh_rs_eval_block(const LhResampler * r, const LhRsBlock * b, int channels, float pcm_scale, float pcm_mix,

@@ -105,6 +105,25 @@ lh_rs_init(LhResampler * r, int rate_in, int rate_out)
         rs_design_kernel(r, ph, cutoff);
 }
 
+/* The converter of a stream the reference does not convert (lh_rs_needed == 0: the input rate is the output rate, or
+ * within 0.05 % of it), for the plans below only: no bank, taps == 0 marks it, and the ratio is the 1 that
+ * lame_encode_flush uses when it does not resample.  Its blocks are what fill_buffer takes (reference util.c:913-920):
+ * min(frame size, samples at hand), made = used. */
+void
+lh_rs_init_identity(LhResampler * r, int rate_in, int rate_out)
+{
+    memset(r, 0, sizeof(*r));
+    r->rate_in = rate_in;
+    r->rate_out = rate_out;
+    r->ratio = 1.0;
+}
+
+int
+lh_rs_is_identity(const LhResampler * r)
+{
+    return r->taps == 0;
+}
+
 /* sample `at' of the channel's virtual sequence: negative positions are the tail kept from the
  * previous blocks (its last sample is position -1) */
 static float
@@ -176,12 +195,14 @@ lh_rs_free(void *p)
     free(p);
 }
 
-/* frames still owed and the end padding once the input is through (fed = output samples so far) */
+/* frames still owed and the end padding once the input is through (fed = output samples so far); ratio 0: a stream that
+ * is not converted, which owes nothing for the converter's delay (reference lame.c:2075-2083) */
 static int
 rs_frames_left(double ratio, int fs, long long fed, int frames, int *padding)
 {
     int     owed = (int) (576 + fed - (long long) fs * frames);
-    owed += 16. / ratio;
+    if (ratio > 0)
+        owed += 16. / ratio;
     *padding = fs - (owed % fs);
     if (*padding < 576)
         *padding += fs;
@@ -321,6 +342,11 @@ static void
 rs_block_extent(const LhResampler * r, double start, int want, int len, int *made, int *taken)
 {
     int     reach = r->taps - r->taps / 2, k;
+    if (lh_rs_is_identity(r)) {
+        /* not converted: fill_buffer's copy */
+        *made = *taken = len < want ? len : want;
+        return;
+    }
     if (want > 0) {
         /* smallest k with rs_reach(k) >= len, i.e. floor(k ratio - start) >= len - taps + taps / 2 */
         double const guess = ceil((len - r->taps + r->taps / 2 + start) / r->ratio);
@@ -505,7 +531,7 @@ int
 lh_rs_plan_flush(const LhResampler * r, int fs, int mfn, LhRsCursor * c, LhRsBlock * blk, int cap, int *padding)
 {
     RsList  list;
-    int     frames_left = rs_frames_left(r->ratio, fs, c->fed, c->frames, padding);
+    int     frames_left = rs_frames_left(lh_rs_is_identity(r) ? 0 : r->ratio, fs, c->fed, c->frames, padding);
     list.blk = blk;
     list.cap = blk ? cap : 0;
     list.n = 0;
@@ -527,16 +553,23 @@ rs_tile_span(const LhResampler * r, double start, int k0, int count)
 int
 lh_rs_block_tiles(const LhResampler * r, const LhRsBlock * b, int stream, LhRsTile * tiles, int cap)
 {
+    return lh_rs_block_tiles_class(r, b, stream, 0, tiles, cap);
+}
+
+int
+lh_rs_block_tiles_class(const LhResampler * r, const LhRsBlock * b, int stream, int cls, LhRsTile * tiles, int cap)
+{
     /* (floor(k ratio - start) is monotone in k, so a tile's span is in its count: an estimate from the ratio, corrected
      * with the exact expression) */
     double const guess = (LH_RS_SPAN_MAX - r->taps - 1) / r->ratio;
+    int const whole = lh_rs_is_identity(r);     /* (a copy stages nothing: the block is one tile) */
     int     k0 = 0, n = 0;
     while (k0 < b->made) {
         int const left = b->made - k0;
-        int     count = guess < 1 ? 1 : guess > left ? left : (int) guess;
-        while (count > 1 && rs_tile_span(r, b->start, k0, count) > LH_RS_SPAN_MAX)
+        int     count = whole ? left : guess < 1 ? 1 : guess > left ? left : (int) guess;
+        while (!whole && count > 1 && rs_tile_span(r, b->start, k0, count) > LH_RS_SPAN_MAX)
             count--;
-        while (count < left && rs_tile_span(r, b->start, k0, count + 1) <= LH_RS_SPAN_MAX)
+        while (!whole && count < left && rs_tile_span(r, b->start, k0, count + 1) <= LH_RS_SPAN_MAX)
             count++;
         if (tiles && n < cap) {
             LhRsTile *t = &tiles[n];
@@ -546,7 +579,7 @@ lh_rs_block_tiles(const LhResampler * r, const LhRsBlock * b, int stream, LhRsTi
             t->k0 = k0;
             t->count = count;
             t->stream = stream;
-            t->pad_ = 0;
+            t->cls = cls;
         }
         n++;
         k0 += count;

@@ -51,7 +51,10 @@ typedef struct LhRsStream {
 /* A tile of an incremental conversion (lh_rs_block_tiles; lh_resample_dev.hip: lh_resample_tiles_kernel): outputs
  * [k0, k0 + count) of the block that starts at clock `start' with its position 0 at in_at go to out_at on (the block's
  * out_at + k0).  A tile is cut so that the input its outputs touch fits LH_RS_SPAN_MAX; lh_rs_locate counts from the
- * block's start, so a block cut into tiles gives the floats of the block done whole. */
+ * block's start, so a block cut into tiles gives the floats of the block done whole.  cls: the tile's rate class, an index
+ * into the class table of lh_resample_mixed_tiles_kernel (a batch whose streams arrive at rates of their own); the
+ * single-rate kernel never reads it.  A tile of a class that is not converted (LhRsClass.identity) is its whole block:
+ * k0 = 0, outputs [out_at, out_at + count) are inputs [in_at, in_at + count) behind the PCM matrix. */
 typedef struct LhRsTile {
     long long in_at;
     long long out_at;
@@ -59,8 +62,21 @@ typedef struct LhRsTile {
     int     k0;
     int     count;
     int     stream;             /* row pair of the pools, and the entry of the launch's table of input lengths */
-    int     pad_;
+    int     cls;
 } LhRsTile;
+
+/* A rate class of a mixed conversion: what lh_rs_locate needs, and where the class's bank of kernels starts in the one
+ * allocation that holds all banks (in floats, a multiple of 4: rows of LH_RS_ROW floats on 16-byte boundaries).
+ * identity: the class's rate is the output rate, as far as the reference cares (lh_rs_needed): no bank. */
+typedef struct LhRsClass {
+    double  ratio;
+    int     taps;
+    int     phases;
+    int     identity;
+    long long bank_at;
+} LhRsClass;
+
+#define LH_RS_CLASSES_MAX 16   /* distinct input rates alive in one batch */
 
 #define LH_RS_ROW 36           /* floats per kernel of the device's bank in HBM: rows start on 16-byte boundaries */
 /* input positions a block's outputs can touch: its len <= 1152 samples and the taps + 1 <= 33 before them */

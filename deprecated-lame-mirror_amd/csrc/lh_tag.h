@@ -44,6 +44,7 @@
 #define LH_TAG_AT_EXT 116       /* the LAME extension (reference PutLameVBR) ... */
 #define LH_TAG_EXT_GAIN 19      /* ... and in it: the radio ReplayGain field, */
 #define LH_TAG_EXT_PADDING 25   /* encoder delay and end padding, 12 bits each, */
+#define LH_TAG_EXT_INFO 28      /* the info byte: noise shaping, stereo mode, "non-optimal" and the source frequency, */
 #define LH_TAG_EXT_LENGTH 32    /* the music's length, */
 #define LH_TAG_EXT_MUSIC_CRC 36 /* its CRC, */
 #define LH_TAG_EXT_CRC 38       /* and the CRC of the frame up to here */
@@ -91,6 +92,29 @@ typedef struct LhTagCarry {
 typedef struct LhTagPow {
     uint16_t col[LH_TAG_NPOW][16];
 } LhTagPow;
+
+/* A stream of an incremental batch whose input rate is its own (lamehip_batch_set_stream_in_samplerate) has its own info
+ * byte -- the source frequency and the "non-optimal" bit are made of the input rate, lh_tag_template --, which travels with
+ * the stream's end padding (12 bits) in the table the final step of lh_tag_resume_kernel reads: bit 24 says there is one,
+ * bits 16 .. 23 are the byte.  The step puts it into the template's copy before the frame's CRCs are taken. */
+LH_TAG_FN int
+lh_tag_pad_with_info(int enc_padding, int info)
+{
+    return (enc_padding & 0xffff) | ((info & 0xff) << 16) | (1 << 24);
+}
+
+LH_TAG_FN int
+lh_tag_pad_padding(int entry)
+{
+    return entry & 0xffff;
+}
+
+/* the info byte of a table entry, or -1: the template's */
+LH_TAG_FN int
+lh_tag_pad_info(int entry)
+{
+    return ((entry >> 24) & 1) ? ((entry >> 16) & 0xff) : -1;
+}
 
 /* one byte into the music CRC (reflected polynomial 0xA001, reference VbrTag.c:73-122) without a table: the byte's eight
  * steps shift its bits out through taps 0, 13 and 15 -- each bit lands 6 and 7 places up, and their parity on both ends */

@@ -177,10 +177,11 @@ tag_bag(const LhTagParams & p, const LhFrameOut * fr, int n, LhTagLds & lds, int
 }
 
 /* C: the frame in LDS from the bag there -- the template, the seek table's 99 entries a lane each, the other fields in lane
- * 0 (which holds the music CRC) --, and out to `tag' */
+ * 0 (which holds the music CRC) --, and out to `tag'.  info: the stream's own info byte (lh_tag.h: lh_tag_pad_info), which
+ * takes the template's place before the CRCs are taken, or -1 */
 LH_TAG_FN void
 tag_frame_out(const LhTagParams & p, const unsigned char *tmpl, int pos, int sum, uint32_t nf, long long n, uint32_t crc, int enc_padding,
-              int last_mode_ext, unsigned char *tag, LhTagLds & lds)
+              int info, int last_mode_ext, unsigned char *tag, LhTagLds & lds)
 {
     int const tid = (int) threadIdx.x;
     for (int i = tid; i < p.total; i += LH_TAG_NT)
@@ -188,6 +189,8 @@ tag_frame_out(const LhTagParams & p, const unsigned char *tmpl, int pos, int sum
     __syncthreads();
     if (tid >= 1 && tid < 100)
         lds.frame[p.at + LH_TAG_AT_TOC + tid] = lh_tag_toc_entry(tid, lds.bag, pos, sum);
+    if (tid == 0 && info >= 0)
+        lds.frame[p.at + LH_TAG_AT_EXT + LH_TAG_EXT_INFO] = (unsigned char) info;
     __syncthreads();
     if (tid == 0)
         lh_tag_finish_fields(lds.frame, p.at, p.sideinfo_len, p.error_protection, nf, (uint32_t) (n + p.total), crc, enc_padding,
@@ -211,7 +214,7 @@ tag_stream(const LhTagParams & p, const unsigned char *audio, long long n, const
     }
     uint32_t const crc = tag_music_crc(p, audio, n, lds);
     tag_bag(p, fr, nf, lds, &pos, &want, &sum);
-    tag_frame_out(p, tmpl, pos, sum, (uint32_t) nf, n, crc, enc_padding, fr[nf - 1].mode_ext, tag, lds);
+    tag_frame_out(p, tmpl, pos, sum, (uint32_t) nf, n, crc, enc_padding, -1, fr[nf - 1].mode_ext, tag, lds);
 }
 
 /* grid: one workgroup per stream.  descs / states: the launch's; out: its records; bytes: the pool, in which stream s's
@@ -235,10 +238,11 @@ lh_tag_kernel(LhTagParams p, const LhStreamDesc * descs, const LhStreamState * s
 
 /* One stream of an incremental batch, one round: the carry *c moved on over the bytes [c->crc_upto, upto) of `slice' and the
  * round's nf records, and behind the flush (`final') the frame to `tag'.  Nothing of the slice at or behind `upto' is read:
- * the reservoir still back-fills there.  bad_now: the round found the stream with a status or an impossible position. */
+ * the reservoir still back-fills there.  bad_now: the round found the stream with a status or an impossible position.
+ * pad_entry: the stream's entry of the padding table -- its end padding, and its own info byte if it has one (lh_tag.h). */
 LH_TAG_FN void
 tag_resume(const LhTagParams & p, const LhTagPow * pw, const unsigned char *slice, long long upto, int bad_now, const LhFrameOut * fr, int nf,
-           int final, int enc_padding, const unsigned char *tmpl, LhTagCarry * c, unsigned char *tag, LhTagLds & lds)
+           int final, int pad_entry, const unsigned char *tmpl, LhTagCarry * c, unsigned char *tag, LhTagLds & lds)
 {
     int const tid = (int) threadIdx.x;
     long long const from = c->crc_upto;
@@ -297,7 +301,7 @@ tag_resume(const LhTagParams & p, const LhTagPow * pw, const unsigned char *slic
             tag[i] = 0;
         return;
     }
-    tag_frame_out(p, tmpl, pos1, sum1, (uint32_t) n1, upto, crc, enc_padding, mode_ext, tag, lds);
+    tag_frame_out(p, tmpl, pos1, sum1, (uint32_t) n1, upto, crc, lh_tag_pad_padding(pad_entry), lh_tag_pad_info(pad_entry), mode_ext, tag, lds);
 }
 
 /* grid: one workgroup per stream, behind a round's drain.  descs / states: the round's; rows: the drain's table (upto: the

@@ -590,6 +590,24 @@ class Batch:
         if rc:
             raise RuntimeError("lamehip_batch_set_incremental_resampling failed (%d): %s" % (rc, last_error()))
 
+    def set_stream_in_samplerate(self, s, hz):
+        """Stream s arrives at hz (a batch with set_incremental_resampling(), before the stream's first sample): its bytes,
+        frames, padding, tag frame and gain are those of a reference handle with in = hz and the batch's output rate given
+        explicitly.  All rates of a round are converted by one launch (resample_ms()); reset() and restart_stream() put a
+        stream back at the batch's own rate."""
+        self.lib.lamehip_batch_set_stream_in_samplerate.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        rc = self.lib.lamehip_batch_set_stream_in_samplerate(self.b, s, hz)
+        if rc:
+            raise RuntimeError("lamehip_batch_set_stream_in_samplerate failed (%d): %s" % (rc, last_error()))
+
+    def stream_in_samplerate(self, s):
+        """The input rate of stream s: the batch's own unless set_stream_in_samplerate() stated another."""
+        self.lib.lamehip_batch_stream_in_samplerate.argtypes = [C.c_void_p, C.c_int]
+        hz = self.lib.lamehip_batch_stream_in_samplerate(self.b, s)
+        if hz < 0:
+            raise RuntimeError("lamehip_batch_stream_in_samplerate: no stream %d" % s)
+        return int(hz)
+
     def converted(self, s):
         """The converted signal of stream s as the encoder reads it: float32 [2, converted length] (test accessor)."""
         self.lib.lamehip_batch_get_converted.restype = C.c_long
@@ -597,6 +615,8 @@ class Batch:
         cap = max((self.frames(s) + 4) * 1152, self.capacity)    # (an incremental batch knows its frames at finish())
         h = getattr(self.enc, "h", None)
         rate_in, rate_out = (self.lib.lame_get_in_samplerate(h), self.lib.lame_get_out_samplerate(h)) if h else (0, 0)
+        if h and hasattr(self.lib, "lamehip_batch_stream_in_samplerate"):
+            rate_in = min(rate_in, self.stream_in_samplerate(s))      # (the stream's own rate, where it has one)
         if 0 < rate_in < rate_out:     # (one that converts upwards holds more than its capacity of input samples)
             cap = max(cap, self.capacity * rate_out // rate_in + 4 * 1152 + 64)
         out = np.zeros((2, cap), dtype=np.float32)

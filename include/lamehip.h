@@ -267,6 +267,38 @@ int     lamehip_batch_set_device_resampling(lamehip_batch *, int on);
  * lamehip_batch_set_incremental_replaygain.  Until the first append the batch takes whole streams as before.
  * An allocation failure returns LAMEHIP_ERR_DEVICE and leaves the batch as it was. */
 int     lamehip_batch_set_incremental_resampling(lamehip_batch *, int on);
+/* Every stream at its own input rate: a pool of slots fed at 8, 16, 22.05, 32, 44.1, 48, 96 kHz ... that all come out as the
+ * batch's one kind of MP3.  lamehip_batch_set_stream_in_samplerate tells a batch that converts round by round (both switches
+ * above on) that stream s arrives at hz.  From then on the stream's bytes, frames, end padding, tag frame
+ * (lamehip_batch_set_incremental_tagging: the info byte's source-frequency and "non-optimal" bits are the stream's) and
+ * radio gain are those of a reference handle with the batch's settings, lame_set_in_samplerate(hz) and
+ * lame_set_out_samplerate(R) given explicitly, R the batch's resolved output rate, fed the same calls -- each append one
+ * lame_encode_buffer* call, as on any such batch.  A rate the reference does not convert (within +-0.05 % of R:
+ * 44 077 .. 44 122 Hz for 44.1 kHz) is not converted here either: the samples pass the PCM matrix only.
+ *   accepted rates   any hz > 0 for which the library's host init resolves the batch's configuration and tables again with
+ *                    (in = hz, out = R explicit, every other setting the handle's); the resolved records are compared, and
+ *                    -1 names the record and the byte that differs
+ *   when             the stream has nothing appended yet: a fresh batch, after lamehip_batch_reset, after
+ *                    lamehip_batch_restart_stream and before the first append; -1 otherwise.  lamehip_batch_reset and
+ *                    lamehip_batch_restart_stream put a stream back at the batch's own rate: a slot's next tenant states
+ *                    its rate again
+ *   capacity         still counts input samples per stream at whatever rate; the float pool's rows stay what the batch's own
+ *                    rate gives them, so a stream at a lower rate fills its row sooner, and the appends' refusal ("flushed
+ *                    behind this call, would be ... converted samples") is computed with the stream's own converter
+ *   classes          distinct rates alive in a batch are classes, 16 at most, the batch's own rate one of them; a class -- its
+ *                    converter and its bank of kernels in HBM -- is made on first use and lives until lamehip_batch_destroy;
+ *                    one more is refused (-1); an allocation failure returns LAMEHIP_ERR_DEVICE and leaves the batch as it
+ *                    was
+ *   refused (-1, lamehip_last_error() names the call)   a batch without lamehip_batch_set_incremental_resampling, a finished
+ *                    batch, no such stream, hz <= 0, a stream that has samples or has ended -- and, once any stream has a
+ *                    rate other than the batch's, lamehip_batch_set_pcm*, _set_input*, _set_length and lamehip_batch_encode:
+ *                    the one-shot converter shares one trunk of blocks between all streams and stays single-rate
+ * A round with such a stream converts all rates in ONE launch (csrc/lh_resample_dev.hip: lh_resample_mixed_tiles_kernel,
+ * timed by lamehip_batch_last_resample_ms as before); a batch that never makes the call gets the launches, kernels, layouts
+ * and bytes it always got.  lamehip_batch_stream_in_samplerate returns the stream's rate, the batch's own when none was
+ * set; -1: no such stream. */
+int     lamehip_batch_set_stream_in_samplerate(lamehip_batch *, int stream, int hz);
+int     lamehip_batch_stream_in_samplerate(lamehip_batch *, int stream);
 /* test accessor: the converted signal of a stream (float planes as the encoder reads them), valid after
  * lamehip_batch_set_pcm when the host converts and after lamehip_batch_encode when the device does -- also the float
  * planes of a batch of another sample type that does not convert, after lamehip_batch_encode, or, on an incremental
