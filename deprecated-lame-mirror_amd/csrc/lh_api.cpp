@@ -564,7 +564,7 @@ lame_bitrate_hist(const lame_t g, int bitrate_count[14])
 {
     if (valid(g) && g->inited)
         for (int i = 0; i < 14; i++)
-            bitrate_count[i] = g->hist_mode[i + 1][4];
+            bitrate_count[i] = g->hist.mode[i + 1][4];
 }
 
 extern "C" void
@@ -572,7 +572,7 @@ lame_stereo_mode_hist(const lame_t g, int stmode_count[4])
 {
     if (valid(g) && g->inited)
         for (int i = 0; i < 4; i++)
-            stmode_count[i] = g->hist_mode[15][i];
+            stmode_count[i] = g->hist.mode[15][i];
 }
 
 extern "C" void
@@ -581,7 +581,7 @@ lame_bitrate_stereo_mode_hist(const lame_t g, int bitrate_stmode_count[14][4])
     if (valid(g) && g->inited)
         for (int j = 0; j < 14; j++)
             for (int i = 0; i < 4; i++)
-                bitrate_stmode_count[j][i] = g->hist_mode[j + 1][i];
+                bitrate_stmode_count[j][i] = g->hist.mode[j + 1][i];
 }
 
 extern "C" void
@@ -589,7 +589,7 @@ lame_block_type_hist(const lame_t g, int btype_count[6])
 {
     if (valid(g) && g->inited)
         for (int i = 0; i < 6; i++)
-            btype_count[i] = g->hist_block[15][i];
+            btype_count[i] = g->hist.block[15][i];
 }
 
 extern "C" void
@@ -598,7 +598,7 @@ lame_bitrate_block_type_hist(const lame_t g, int bitrate_btype_count[14][6])
     if (valid(g) && g->inited)
         for (int j = 0; j < 14; j++)
             for (int i = 0; i < 6; i++)
-                bitrate_btype_count[j][i] = g->hist_block[j + 1][i];
+                bitrate_btype_count[j][i] = g->hist.block[j + 1][i];
 }
 GETTER(lame_get_version, g->inited ? g->cfg.version : 1, int)
 
@@ -796,24 +796,8 @@ handle_encode_frames(lame_t g, int upto, unsigned char *mp3buf, int mp3buf_size,
         k = lh_bs_copy(&g->bs, mp3buf + *written, mp3buf_size ? mp3buf_size - *written : 0);
         if (k < 0)
             return -1;
-        {
-            const LhFrameOut & fo = g->h_out[(size_t) i];
-            int const bi = fo.bitrate_index & 15, me = fo.mode_ext & 3;
-            g->hist_mode[bi][4]++;
-            g->hist_mode[15][4]++;
-            if (g->cfg.channels == 2) {
-                g->hist_mode[bi][me]++;
-                g->hist_mode[15][me]++;
-            }
-            for (int gr = 0; gr < 2; gr++)
-                for (int ch = 0; ch < g->cfg.channels; ch++) {
-                    int const bt = fo.gr[gr][ch].mixed_block_flag ? 4 : (fo.gr[gr][ch].block_type & 3);
-                    g->hist_block[bi][bt]++;
-                    g->hist_block[bi][5]++;
-                    g->hist_block[15][bt]++;
-                    g->hist_block[15][5]++;
-                }
-        }
+        /* (updateStats, reference encoder.c:156-184: the granules and channels the stream has, lh_stats.h) */
+        lh_stats_count_frame(&g->hist, &g->h_out[(size_t) i], g->cfg.channels, g->cfg.mode_gr);
         if (g->write_vbr_tag) {
             lh_tag_add_frame(&g->tag, lh_tag_kbps(g->cfg.version, g->h_out[(size_t) i].bitrate_index));  /* reference encoder.c:550-551 */
             lh_tag_crc(&g->tag, mp3buf + *written, k);          /* reference bitstream.c:1082-1088 */
@@ -1144,8 +1128,7 @@ lame_init_bitstream(lame_t g)
     if (!valid(g) || !g->inited)
         return -3;
     g->frame_num_base = g->frames_done;
-    memset(g->hist_mode, 0, sizeof(g->hist_mode));
-    memset(g->hist_block, 0, sizeof(g->hist_block));
+    memset(&g->hist, 0, sizeof(g->hist));
     {
         uint16_t const crc = g->tag.music_crc;  /* the reference's music CRC runs on across the files */
         if (g->write_vbr_tag && lh_tag_init(&g->tag, &g->cfg) > 0) {

@@ -18,6 +18,7 @@
 #include "lh_host.h"
 #include "lh_device.h"
 #include "lh_hip_own.h"
+#include "lh_stats.h"
 
 extern "C" int lh_launch_encode(const LhConfig * cfg, const LhTables * T, const int16_t * pcm, const float *pcmf,
                                 const LhStreamDesc * descs, LhStreamState * states,
@@ -212,8 +213,7 @@ struct lame_global_struct {
     unsigned long num_samples = 0xFFFFFFFFul;   /* MAX_U_32_NUM, reference lame.c:2336 */
     int     preset_vbr = 0;     /* lame_set_preset chose a V0..V9 preset */
     int     frame_num_base = 0; /* frames before the last lame_init_bitstream */
-    int     hist_mode[16][5] = {};      /* [bitrate index | 15 = all][mode extension | 4 = frames] */
-    int     hist_block[16][6] = {};     /* [bitrate index | 15 = all][block type, 4 = mixed | 5 = granules] */
+    LhStatCarry hist = {};      /* mode[bitrate index | 15 = all][mode extension | 4 = frames], block[..][block type, 4 = mixed | 5 = granules] */
     /* (out of line now that the owners make it more than nothing; not a symbol of the library) */
     __attribute__((visibility("hidden"))) ~lame_global_struct() = default;
 };

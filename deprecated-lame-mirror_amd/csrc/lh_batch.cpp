@@ -9,6 +9,7 @@
 #include <atomic>
 
 #include "lh_api_int.h"
+#include "lh_stats.h"
 #include "lh_pcm_in.h"
 #include "lh_gain.h"
 #include "lh_replaygain_tables.h"
@@ -40,6 +41,8 @@ extern "C" int lh_launch_drain(const LhDrainParams * p, const LhStreamDesc * des
 extern "C" int lh_launch_tag_resume(const LhTagParams * p, const LhTagPow * pw, const LhStreamDesc * descs, const LhStreamState * states,
                                     const LhDrainRow * rows, const LhFrameOut * out, const unsigned char *pool, const unsigned char *tmpl,
                                     const int *padding, LhTagCarry * carry, unsigned char *tags, int final, int nstreams, void *stream);
+extern "C" int lh_launch_stats(const LhStreamDesc * descs, const LhFrameOut * out, int nstreams, int channels, int mode_gr, LhStatCarry * carry,
+                               void *stream);
 extern "C" int lh_launch_slot_restart(const int *list, int nlist, int nstreams, LhStreamState * states, const LhStreamState * states0,
                                       long long *drain_carry, LhTagCarry * tag_carry, LhGainCarry * gain_carry, void *stream);
 
@@ -334,6 +337,19 @@ struct lamehip_batch {
     LhDevBuf < LhStreamDesc > d_wdesc;
     std::vector < LhEvent > ev_win;
     int     last_windows = 1;   /* sub-launches of the last launch (1: the whole launch at once) */
+    /* statistics (lamehip_batch_set_statistics): a record per stream in HBM (lh_stats.h: LhStatCarry, the reference's two
+     * tables) that ONE launch of lh_stats_resume_kernel moves on behind every encode launch, a one-shot batch's and a round's
+     * alike, between ev_st[0] and ev_st[1] -- the launch's records are counted where they lie, none comes home for it.  The
+     * getters fetch the whole array on first use after a launch and serve from h_st until the next one.  Nothing of this
+     * exists in a batch without the switch. */
+    int     st_on = 0;
+    LhDevBuf < LhStatCarry > d_st_carry;
+    std::vector < LhStatCarry > h_st;
+    int     st_have = 0;        /* h_st is what d_st_carry holds */
+    LhEvent ev_st[2];
+    int     st_ran = 0;         /* the last launch was followed by the statistics kernel (between ev_st[0] and ev_st[1]) ... */
+    int     st_timed = 0;       /* ... and st_ms is its time */
+    float   st_ms = 0;
 };
 
 enum { LH_SLOT_LIVE = 0, LH_SLOT_ENDING = 1, LH_SLOT_ENDED = 2 };
@@ -527,6 +543,19 @@ batch_launch(lamehip_batch * b, const int16_t * pcm, const float *pcmf, const Lh
     if (rc)
         return set_err("kernel launch", (hipError_t) rc);
     HIPCHK(hipEventRecord(b->ev1, b->stream));
+    b->st_ran = b->st_timed = 0;
+    b->st_ms = 0;
+    if (b->st_on) {
+        /* statistics: the launch's records into the streams' tables, behind the (last window's) encode kernel and outside
+         * ev0 .. ev1; `descs' are the whole launch's whatever the windows, out_index the payload's */
+        HIPCHK(hipEventRecord(b->ev_st[0], b->stream));
+        rc = lh_launch_stats(descs, b->d_out.get(), b->B, b->cfg.channels, b->cfg.mode_gr, b->d_st_carry.get(), stream);
+        if (rc)
+            return set_err("statistics launch", (hipError_t) rc);
+        HIPCHK(hipEventRecord(b->ev_st[1], b->stream));
+        b->st_ran = 1;
+        b->st_have = 0;
+    }
     if (b->ev_wait.create(hipEventDisableTiming) != hipSuccess)
         (void) hipGetLastError();
     if (b->ev_wait)
@@ -602,6 +631,20 @@ static size_t
 batch_pool_bytes(const lamehip_batch * b)
 {
     return (size_t) b->B * 2 * (size_t) b->cap * (size_t) b->esz;
+}
+
+/* statistics: stream s's table in HBM, or all of them (s < 0), zeroed on the batch's stream; the host copy is stale then */
+static int
+batch_stats_zero(lamehip_batch * b, int s)
+{
+    if (!b->st_on)
+        return 0;
+    if (s < 0)
+        HIPCHK(hipMemsetAsync(b->d_st_carry.get(), 0, (size_t) b->B * sizeof(LhStatCarry), b->stream));
+    else
+        HIPCHK(hipMemsetAsync(b->d_st_carry.get() + s, 0, sizeof(LhStatCarry), b->stream));
+    b->st_have = 0;
+    return 0;
 }
 
 /* every stream back to its initial state: a device-to-device copy of the pristine image on the batch's own
@@ -2249,6 +2292,8 @@ batch_encode_range(lamehip_batch * b, const std::vector < int >&upto, int end)
     if (b->inc_rg && (rc = batch_gain_round(b)) != 0)
         return rc;
     if (total == 0) {
+        b->st_ran = b->st_timed = 0;    /* (no statistics launch: the tables stay what they are) */
+        b->st_ms = 0;
         b->dr_ms = 0;           /* (no drain either: what the last round brought home stays where it is) */
         if (b->inc_tag) {
             b->tg_ran = 0;      /* (and no tag launch) */
@@ -2590,6 +2635,11 @@ lamehip_batch_restart_stream(lamehip_batch * b, int s)
         }
         if (lh_bs_init_sized(&fresh, 65536) != 0)
             return -2;
+        /* (statistics: the slot's table alone goes back to zero, on the batch's stream, which the last round has left idle) */
+        if (batch_stats_zero(b, s) != 0) {
+            lh_bs_free(&fresh);
+            return LAMEHIP_ERR_DEVICE;
+        }
         lh_bs_free(&b->packer[(size_t) s]);
         b->packer[(size_t) s] = fresh;
     }
@@ -2645,6 +2695,205 @@ extern "C" float
 lamehip_batch_last_restart_ms(lamehip_batch * b)
 {
     return b ? b->sl_ms : 0.0f;
+}
+
+/* Statistics: the reference's five tables per stream (updateStats), counted on the device behind every encode launch.
+ * Off by default; on any kind of batch, only before any PCM is handed over.  on = 0 puts the batch back as it was. */
+extern "C" int
+lamehip_batch_set_statistics(lamehip_batch * b, int on)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b)
+        return -1;
+    if (b->pcm_given || b->encoded || b->incremental) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_statistics: only before any PCM is handed over");
+        return -1;
+    }
+    if (!on || b->st_on) {
+        b->st_on = on != 0 && b->st_on;
+        return 0;
+    }
+    /* everything new first: a failure leaves the batch as it was */
+    LhDevBuf < LhStatCarry > carry;
+    LhEvent ev[2];
+    std::vector < LhStatCarry > home;
+    hipError_t e = carry.alloc((size_t) b->B);
+    if (e == hipSuccess)
+        e = ev[0].create();
+    if (e == hipSuccess)
+        e = ev[1].create();
+    if (e == hipSuccess)
+        e = hipMemset(carry.get(), 0, (size_t) b->B * sizeof(LhStatCarry));
+    if (e != hipSuccess)
+        return set_err("lamehip_batch_set_statistics", e);
+    try {
+        home.resize((size_t) b->B);
+    }
+    catch(const std::bad_alloc &) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_set_statistics: out of memory");
+        return LAMEHIP_ERR_DEVICE;
+    }
+    b->d_st_carry = std::move(carry);
+    b->ev_st[0] = std::move(ev[0]);
+    b->ev_st[1] = std::move(ev[1]);
+    b->h_st = std::move(home);
+    b->st_have = 0;
+    b->st_ran = b->st_timed = 0;
+    b->st_ms = 0;
+    b->st_on = 1;
+    return 0;
+}
+
+/* HIP-event time in ms of the statistics launch behind the last encode launch; 0 when none was launched (the switch off, a
+ * round without frames).  Not part of lamehip_batch_last_kernel_ms.  Waits for the launch. */
+extern "C" float
+lamehip_batch_last_stats_ms(lamehip_batch * b)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    if (!b || !b->st_on || !b->st_ran)
+        return 0.0f;
+    if (!b->st_timed) {
+        b->st_ms = 0;
+        if (hipEventSynchronize(b->ev_st[1]) != hipSuccess || hipEventElapsedTime(&b->st_ms, b->ev_st[0], b->ev_st[1]) != hipSuccess) {
+            (void) hipGetLastError();
+            b->st_ms = 0;
+        }
+        b->st_timed = 1;
+    }
+    return b->st_ms;
+}
+
+/* the getters' way in: the switch, the stream index (s < 0 with all = true: every stream), and the tables at home -- the
+ * whole array in one copy behind whatever the batch's stream still runs, on first use after a launch */
+static int
+batch_stats_ready(lamehip_batch * b, const char *who, int s, bool all = false)
+{
+    if (!b)
+        return -1;
+    if (!b->st_on) {
+        snprintf(g_err, sizeof(g_err), "%s: the batch keeps no statistics (lamehip_batch_set_statistics)", who);
+        return -1;
+    }
+    if (!all && (s < 0 || s >= b->B)) {
+        snprintf(g_err, sizeof(g_err), "%s: no stream %d (the batch has %d)", who, s, b->B);
+        return -1;
+    }
+    if (!b->st_have) {
+        HIPCHK(hipMemcpyAsync(b->h_st.data(), b->d_st_carry.get(), (size_t) b->B * sizeof(LhStatCarry), hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        b->st_have = 1;
+    }
+    return 0;
+}
+
+/* stream s's two tables as they stand behind the last launch: mode[bitrate index | 15 = all][mode extension | 4 = frames],
+ * block[bitrate index | 15 = all][block type 0..3 | 4 = mixed | 5 = granules] (either may be null) */
+extern "C" int
+lamehip_batch_get_statistics(lamehip_batch * b, int s, int mode[16][5], int block[16][6])
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int const rc = batch_stats_ready(b, "lamehip_batch_get_statistics", s);
+    if (rc)
+        return rc;
+    if (mode)
+        memcpy(mode, b->h_st[(size_t) s].mode, sizeof(b->h_st[0].mode));
+    if (block)
+        memcpy(block, b->h_st[(size_t) s].block, sizeof(b->h_st[0].block));
+    return 0;
+}
+
+/* every stream's: out holds B x 176 ints, a stream's `mode' then its `block' */
+extern "C" int
+lamehip_batch_get_statistics_all(lamehip_batch * b, int *out)
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int const rc = batch_stats_ready(b, "lamehip_batch_get_statistics_all", -1, true);
+    if (rc)
+        return rc;
+    if (!out) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_get_statistics_all: no room given");
+        return -1;
+    }
+    memcpy(out, b->h_st.data(), (size_t) b->B * sizeof(LhStatCarry));
+    return 0;
+}
+
+/* the reference's getters (lame_bitrate_hist and so on), per stream */
+extern "C" int
+lamehip_batch_bitrate_hist(lamehip_batch * b, int s, int bitrate_count[14])
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int const rc = batch_stats_ready(b, "lamehip_batch_bitrate_hist", s);
+    if (rc)
+        return rc;
+    for (int i = 0; i < 14; i++)
+        bitrate_count[i] = b->h_st[(size_t) s].mode[i + 1][4];
+    return 0;
+}
+
+extern "C" int
+lamehip_batch_stereo_mode_hist(lamehip_batch * b, int s, int stmode_count[4])
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int const rc = batch_stats_ready(b, "lamehip_batch_stereo_mode_hist", s);
+    if (rc)
+        return rc;
+    for (int i = 0; i < 4; i++)
+        stmode_count[i] = b->h_st[(size_t) s].mode[15][i];
+    return 0;
+}
+
+extern "C" int
+lamehip_batch_bitrate_stereo_mode_hist(lamehip_batch * b, int s, int bitrate_stmode_count[14][4])
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int const rc = batch_stats_ready(b, "lamehip_batch_bitrate_stereo_mode_hist", s);
+    if (rc)
+        return rc;
+    for (int j = 0; j < 14; j++)
+        for (int i = 0; i < 4; i++)
+            bitrate_stmode_count[j][i] = b->h_st[(size_t) s].mode[j + 1][i];
+    return 0;
+}
+
+extern "C" int
+lamehip_batch_block_type_hist(lamehip_batch * b, int s, int btype_count[6])
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int const rc = batch_stats_ready(b, "lamehip_batch_block_type_hist", s);
+    if (rc)
+        return rc;
+    for (int i = 0; i < 6; i++)
+        btype_count[i] = b->h_st[(size_t) s].block[15][i];
+    return 0;
+}
+
+extern "C" int
+lamehip_batch_bitrate_block_type_hist(lamehip_batch * b, int s, int bitrate_btype_count[14][6])
+{
+    LhDeviceScope const on_device(b ? b->device : -1);
+    int const rc = batch_stats_ready(b, "lamehip_batch_bitrate_block_type_hist", s);
+    if (rc)
+        return rc;
+    for (int j = 0; j < 14; j++)
+        for (int i = 0; i < 6; i++)
+            bitrate_btype_count[j][i] = b->h_st[(size_t) s].block[j + 1][i];
+    return 0;
+}
+
+/* the bit rates the rows 1..14 stand for (lame_bitrate_kbps) */
+extern "C" int
+lamehip_batch_bitrate_kbps(lamehip_batch * b, int bitrate_kbps[14])
+{
+    if (!b)
+        return -1;
+    if (!b->st_on) {
+        snprintf(g_err, sizeof(g_err), "lamehip_batch_bitrate_kbps: the batch keeps no statistics (lamehip_batch_set_statistics)");
+        return -1;
+    }
+    for (int i = 0; i < 14; i++)
+        bitrate_kbps[i] = lh_tag_kbps(b->cfg.version, i + 1);
+    return 0;
 }
 
 /* bytes of stream s produced since the last drain; -1 (and nothing taken) when they do not fit */
@@ -2766,6 +3015,11 @@ lamehip_batch_reset(lamehip_batch * b)
     for (std::vector < double >&w:b->rg_win)
         w.clear();
     b->rg_dirty.assign((size_t) b->B, 1);
+    /* (and every count) */
+    if (batch_stats_zero(b, -1) != 0)
+        return LAMEHIP_ERR_DEVICE;
+    b->st_ran = b->st_timed = 0;
+    b->st_ms = 0;
     return batch_reset_states(b);
 }
 
@@ -3451,6 +3705,9 @@ lamehip_batch_encode(lamehip_batch * b)
         if (rc)
             return rc;
     }
+    /* statistics: every call counts the streams from their first frame */
+    if (b->st_on && batch_stats_zero(b, -1) != 0)
+        return LAMEHIP_ERR_DEVICE;
     /* (what the launch will be -- and the pool it needs -- before the device's launch order is taken: an allocation of tens
      * of GB must not keep other batches' launches waiting) */
     LhLaunchPlan plan;

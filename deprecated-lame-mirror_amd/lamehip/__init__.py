@@ -437,6 +437,70 @@ class Batch:
         self.lib.lamehip_batch_last_restart_ms.argtypes = [C.c_void_p]
         return float(self.lib.lamehip_batch_last_restart_ms(self.b))
 
+    def set_statistics(self, on=True):
+        """Keep the reference's per-stream statistics (bit rate / stereo mode / block type histograms), counted on the device
+        behind every encode launch (csrc/lh_stats.hip).  Before any PCM is handed over."""
+        self.lib.lamehip_batch_set_statistics.argtypes = [C.c_void_p, C.c_int]
+        rc = self.lib.lamehip_batch_set_statistics(self.b, 1 if on else 0)
+        if rc != 0:
+            raise RuntimeError("lamehip_batch_set_statistics failed (%d): %s" % (rc, last_error()))
+
+    def _stat_call(self, name, *args):
+        fn = getattr(self.lib, name)
+        fn.argtypes = [C.c_void_p] + [C.c_int if isinstance(a, int) else C.c_void_p for a in args]
+        rc = fn(self.b, *[a if isinstance(a, int) else a.ctypes.data for a in args])
+        if rc != 0:
+            raise RuntimeError("%s failed (%d): %s" % (name, rc, last_error()))
+
+    def statistics(self, s):
+        """(mode[16, 5], block[16, 6]) of stream s behind the last launch: mode[bitrate index | 15 = all][mode extension |
+        4 = frames], block[bitrate index | 15 = all][block type 0..3 | 4 = mixed | 5 = granules]."""
+        mode, block = np.zeros((16, 5), np.int32), np.zeros((16, 6), np.int32)
+        self._stat_call("lamehip_batch_get_statistics", int(s), mode, block)
+        return mode, block
+
+    def statistics_all(self):
+        """Every stream's tables, [B, 176]: a stream's mode[16, 5] then its block[16, 6]."""
+        out = np.zeros((self.n, 176), np.int32)
+        self._stat_call("lamehip_batch_get_statistics_all", out)
+        return out
+
+    def bitrate_kbps(self):
+        """The bit rates that entries 0..13 of bitrate_hist() stand for."""
+        out = np.zeros(14, np.int32)
+        self._stat_call("lamehip_batch_bitrate_kbps", out)
+        return out
+
+    def bitrate_hist(self, s):
+        """Frames of stream s per bit rate (lame_bitrate_hist)."""
+        out = np.zeros(14, np.int32)
+        self._stat_call("lamehip_batch_bitrate_hist", int(s), out)
+        return out
+
+    def stereo_mode_hist(self, s):
+        """Frames of stream s per stereo mode: LR, LR-i, MS, MS-i (lame_stereo_mode_hist)."""
+        out = np.zeros(4, np.int32)
+        self._stat_call("lamehip_batch_stereo_mode_hist", int(s), out)
+        return out
+
+    def block_type_hist(self, s):
+        """Granules of stream s per block type: long, start, short, stop, mixed, all (lame_block_type_hist)."""
+        out = np.zeros(6, np.int32)
+        self._stat_call("lamehip_batch_block_type_hist", int(s), out)
+        return out
+
+    def average_kbps(self, s):
+        """sum(kbps[i] * frames[i]) / frames of stream s, the figure the reference's frontend prints; 0.0 without frames."""
+        hist = self.bitrate_hist(s).astype(np.int64)
+        n = int(hist.sum())
+        return float((self.bitrate_kbps().astype(np.int64) * hist).sum()) / n if n else 0.0
+
+    def stats_ms(self):
+        """HIP-event time of the statistics launch behind the last encode launch; 0 when there was none."""
+        self.lib.lamehip_batch_last_stats_ms.restype = C.c_float
+        self.lib.lamehip_batch_last_stats_ms.argtypes = [C.c_void_p]
+        return float(self.lib.lamehip_batch_last_stats_ms(self.b))
+
     def drain(self, s, cap=1 << 20):
         """Bytes stream s has produced since its last drain."""
         self.lib.lamehip_batch_drain.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]

@@ -520,6 +520,40 @@ int     lamehip_batch_end_stream(lamehip_batch *, int stream);
 int     lamehip_batch_stream_ended(lamehip_batch *, int stream);     /* 1 ended, 0 not, -1 bad argument */
 int     lamehip_batch_restart_stream(lamehip_batch *, int stream);
 float   lamehip_batch_last_restart_ms(lamehip_batch *);
+
+/* Statistics: what the reference keeps per stream and its frontend prints after every file (updateStats; lame_bitrate_hist,
+ * lame_stereo_mode_hist, lame_bitrate_stereo_mode_hist, lame_block_type_hist, lame_bitrate_block_type_hist), for every
+ * stream of a batch, counted on the device: behind every encode launch -- lamehip_batch_encode's, and every round's of an
+ * incremental batch -- one small kernel (lh_stats.hip) adds the launch's frame records, where they lie in HBM, to a table of
+ * 176 ints per stream.  No record comes home for it; a getter fetches the tables (704 bytes per stream) once after a launch.
+ *   lamehip_batch_set_statistics  off by default; on any kind of batch (one-shot or incremental, host or device packing,
+ *                                 with or without incremental packing, tagging, ReplayGain or resampling, any sample type).
+ *                                 -1 once PCM, a length or an append has been handed over.  Off: nothing is allocated or
+ *                                 launched.
+ *   lamehip_batch_get_statistics  stream s's tables as they stand behind the last launch (the getters wait for it):
+ *                                 mode[bitrate index | 15 = all][mode extension 0..3 | 4 = frames] and
+ *                                 block[bitrate index | 15 = all][block type 0..3 | 4 = mixed | 5 = granules]; either may
+ *                                 be null.  An incremental batch: the frames of the rounds so far, lamehip_batch_frames of
+ *                                 them after lamehip_batch_finish.  lamehip_batch_encode counts from zero every time, as
+ *                                 does a batch after lamehip_batch_reset; a stream that ended (lamehip_batch_end_stream)
+ *                                 keeps its counts until lamehip_batch_restart_stream zeroes them, its slot's alone.
+ *   lamehip_batch_get_statistics_all  every stream's: B x 176 ints, a stream's mode[16][5] then its block[16][6].
+ *   lamehip_batch_bitrate_hist ... _bitrate_block_type_hist  the reference's getters with (batch, stream) in front.
+ *   lamehip_batch_bitrate_kbps    the bit rates of rows 1..14 (lame_bitrate_kbps).
+ *   lamehip_batch_last_stats_ms   HIP-event time in ms of the statistics launch behind the last encode launch; 0 when there
+ *                                 was none.  Not part of lamehip_batch_last_kernel_ms.
+ * Every getter returns 0, or -1 without the switch or for a stream the batch does not have (lamehip_last_error() names the
+ * call). */
+int     lamehip_batch_set_statistics(lamehip_batch *, int on);
+int     lamehip_batch_get_statistics(lamehip_batch *, int stream, int mode[16][5], int block[16][6]);
+int     lamehip_batch_get_statistics_all(lamehip_batch *, int *out);
+int     lamehip_batch_bitrate_hist(lamehip_batch *, int stream, int bitrate_count[14]);
+int     lamehip_batch_stereo_mode_hist(lamehip_batch *, int stream, int stereo_mode_count[4]);
+int     lamehip_batch_bitrate_stereo_mode_hist(lamehip_batch *, int stream, int bitrate_stmode_count[14][4]);
+int     lamehip_batch_block_type_hist(lamehip_batch *, int stream, int btype_count[6]);
+int     lamehip_batch_bitrate_block_type_hist(lamehip_batch *, int stream, int bitrate_btype_count[14][6]);
+int     lamehip_batch_bitrate_kbps(lamehip_batch *, int bitrate_kbps[14]);
+float   lamehip_batch_last_stats_ms(lamehip_batch *);
 /* encode every stream completely (all frames incl. the flush frames), payload
  * stays in HBM; asynchronous on the batch's HIP stream */
 int     lamehip_batch_encode(lamehip_batch *);
