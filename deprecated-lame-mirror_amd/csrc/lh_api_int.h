@@ -46,11 +46,15 @@ extern "C" int lh_launch_encode_vbr(const LhConfig * cfg, const LhTables * T, co
                                           const LhStreamDesc * descs, LhStreamState * states, LhMidPools mid, \
                                           int nstreams, int max_frames, void *stream);
 LH_DECL_SPLIT()
+/* the front masking kernels of a CBR / ABR launch (lh_psy_finish.hip; MPEG-1 streams), behind the analysis kernels */
+extern "C" int lh_launch_psy_finish(const LhConfig * cfg, const LhTables * T, const LhStreamDesc * descs, const LhStreamState * states,
+                                    LhMidPools mid, LhMidPsy * psy, int nstreams, int max_frames, void *stream);
 LH_DECL_SPLIT(_lsf)
 #define LH_DECL_Q(sfx) \
     extern "C" int lh_launch_encode_q##sfx(const LhConfig * cfg, const LhTables * T, const int16_t * pcm, const float *pcmf, \
                                            const LhStreamDesc * descs, LhStreamState * states, LhFrameOut * out, \
-                                           uint8_t * bytes, int nstreams, void *stream, LhMidPools mid);
+                                           uint8_t * bytes, int nstreams, void *stream, LhMidPools mid, \
+                                           const LhMidPsy * psy);
 LH_DECL_Q()
 LH_DECL_Q(_vbr)
 LH_DECL_Q(_lsf)
@@ -104,20 +108,29 @@ struct LhDeviceConst {
     LhTables *d_tab = nullptr;
     int     lsf = 0;            /* an MPEG-2 / 2.5 stream: the kernel object compiled for one granule per frame */
     int     vbrk = 0;           /* an MPEG-1 stream in the new VBR loop: the object scheduled for that loop */
+    int     front = 0;          /* an MPEG-1 stream in the CBR or ABR loop: its split launches run the front masking kernels */
+    int front_psy() const { return front; }
     int launch(const int16_t * pcm, const float *pcmf, const LhStreamDesc * descs, LhStreamState * states,
                LhFrameOut * out, uint8_t * bytes, int nstreams, void *stream) const {
         return (lsf ? lh_launch_encode_lsf : vbrk ? lh_launch_encode_vbr : lh_launch_encode)
             (d_cfg, d_tab, pcm, pcmf, descs, states, out, bytes, nstreams, stream);
     }
     /* The split pipeline: analysis kernels for every frame of the launch, then the encode kernel that starts from what they
-     * left in `mid'.  ev[0..1], when given, are recorded behind the analysis and the sub-band kernels (per-kernel times). */
+     * left in `mid'.  ev[0..1], when given, are recorded behind the analysis and the sub-band kernels (per-kernel times).  psy,
+     * when not null (front_psy() says whether a launch may have one): the front masking kernels run behind the analysis kernels
+     * -- their time counts as analysis -- and the encode kernel starts from their records. */
     int launch_split(const int16_t * pcm, const float *pcmf, const LhStreamDesc * descs, LhStreamState * states,
-                     LhFrameOut * out, uint8_t * bytes, int nstreams, int max_frames, const LhMidPools & mid, void *stream,
+                     LhFrameOut * out, uint8_t * bytes, int nstreams, int max_frames, const LhMidPools & mid, LhMidPsy * psy, void *stream,
                      hipEvent_t * ev) const {
         int     rc;
         rc = (lsf ? lh_launch_analysis_lsf : lh_launch_analysis) (d_cfg, d_tab, pcm, pcmf, descs, states, mid, nstreams, max_frames, stream);
         if (rc)
             return rc;
+        if (psy) {
+            rc = lh_launch_psy_finish(d_cfg, d_tab, descs, states, mid, psy, nstreams, max_frames, stream);
+            if (rc)
+                return rc;
+        }
         if (ev) {
             hipError_t const e = hipEventRecord(ev[0], (hipStream_t) stream);
             if (e != hipSuccess)
@@ -132,11 +145,12 @@ struct LhDeviceConst {
                 return (int) e;
         }
         return (lsf ? lh_launch_encode_q_lsf : vbrk ? lh_launch_encode_q_vbr : lh_launch_encode_q)
-            (d_cfg, d_tab, pcm, pcmf, descs, states, out, bytes, nstreams, stream, mid);
+            (d_cfg, d_tab, pcm, pcmf, descs, states, out, bytes, nstreams, stream, mid, psy);
     }
     int upload(const LhConfig & cfg, const LhTables & tab) {
         lsf = (cfg.mode_gr == 1);
         vbrk = !lsf && (cfg.vbr == 1 || cfg.vbr == 4);
+        front = !lsf && (cfg.vbr == 0 || cfg.vbr == 3);
         HIPCHK(hipMalloc((void **) &d_cfg, sizeof(LhConfig)));
         HIPCHK(hipMalloc((void **) &d_tab, sizeof(LhTables)));
         HIPCHK(hipMemcpy(d_cfg, &cfg, sizeof(LhConfig), hipMemcpyHostToDevice));

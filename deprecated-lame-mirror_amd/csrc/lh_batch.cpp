@@ -324,6 +324,9 @@ struct lamehip_batch {
     int     launched = 0;       /* a kernel was launched on this batch and ev1 recorded (survives lamehip_batch_reset) */
     /* the split pipeline's pool (one record per frame of a launch, like d_out) and the events between its kernels */
     LhDevBuf < LhMidFrame > mid;
+    /* the front masking kernels' records beside them, same index and as many (a batch whose launches run them: CBR / ABR,
+     * MPEG-1; LhDeviceConst::front_psy) */
+    LhDevBuf < LhMidPsy > midpsy;
     int     split = 0;          /* this batch's launches go through the split pipeline (batch_use_split) */
     LhEvent ev_part[2];
     LhEvent ev_wait;            /* behind the launch; only ever polled (hipEventQuery between short sleeps in lamehip_batch_sync): the
@@ -373,12 +376,14 @@ batch_mid_reserve(lamehip_batch * b, long long need, long long *free_records = n
      * read past the pool) */
     if (free_records)
         *free_records = 0;
-    if (need + 1 <= (long long) b->mid.cap())
+    size_t const rec_b = sizeof(LhMidFrame) + (b->dc.front_psy() ? sizeof(LhMidPsy) : 0);      /* per frame, both pools */
+    if (need + 1 <= (long long) b->mid.cap() && (!b->dc.front_psy() || b->midpsy.cap() == b->mid.cap()))
         return 0;
     size_t  free_b = 0, total_b = 0;
     long long const want = need + 64;
-    /* (the old pool goes first, unlike LhDevBuf::reserve: what it held counts as free for the new one) */
+    /* (the old pools go first, unlike LhDevBuf::reserve: what they held counts as free for the new ones) */
     b->mid.release();
+    b->midpsy.release();
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess)
         free_b = 0;
     {
@@ -390,17 +395,18 @@ batch_mid_reserve(lamehip_batch * b, long long need, long long *free_records = n
             free_b = (size_t) mb * 1000000u;
     }
     if (free_records)
-        *free_records = (long long) (0.8 * (double) free_b / (double) sizeof(LhMidFrame)) - 64;
-    if ((double) want * (double) sizeof(LhMidFrame) > 0.8 * (double) free_b) {
+        *free_records = (long long) (0.8 * (double) free_b / (double) rec_b) - 64;
+    if ((double) want * (double) rec_b > 0.8 * (double) free_b) {
         /* (not an error: the launch runs in windows or takes the fused kernel; lamehip_last_error() says why) */
         snprintf(g_err, sizeof(g_err), "split pipeline: %lld frames need %.1f GB of analysis records, %.1f GB free",
-                 need, (double) want * (double) sizeof(LhMidFrame) / 1e9, (double) free_b / 1e9);
+                 need, (double) want * (double) rec_b / 1e9, (double) free_b / 1e9);
         return -1;
     }
-    if (b->mid.alloc((size_t) want) != hipSuccess) {
+    if (b->mid.alloc((size_t) want) != hipSuccess || (b->dc.front_psy() && b->midpsy.alloc((size_t) want) != hipSuccess)) {
         (void) hipGetLastError();
+        b->mid.release();
         snprintf(g_err, sizeof(g_err), "split pipeline: hipMalloc of %.1f GB of analysis records failed",
-                 (double) want * (double) sizeof(LhMidFrame) / 1e9);
+                 (double) want * (double) rec_b / 1e9);
         return -1;
     }
     return 0;
@@ -433,7 +439,7 @@ batch_window_records(const lamehip_batch * b, const LhStreamDesc * h_descs, int 
 }
 
 /* What the launch of the frames `h_descs' names will be: the split pipeline over the whole launch when its analysis records
- * fit the device (34 KB per frame: 81 GB at 1024 x 60 s), else the split pipeline over windows of as many frames per stream as
+ * fit the device (34 KB per frame, 38 KB with the front masking kernels' records: 90 GB at 1024 x 60 s), else the split pipeline over windows of as many frames per stream as
  * do fit -- each window a launch of its own, analysis kernels then encode kernel, the streams' state carried in
  * LhStreamState as between two launches of an incremental batch --, else (under LH_MID_WINDOW_MIN frames per window, more
  * than 65 535 streams, LAMEHIP_FUSED / LAMEHIP_SPLIT_DENY) the fused kernel.  The windows' descriptors go to HBM here, on the
@@ -520,6 +526,7 @@ batch_launch(lamehip_batch * b, const int16_t * pcm, const float *pcmf, const Lh
     int     rc = 0, split = p.split;
     void   *const stream = (void *) (hipStream_t) b->stream;
     LhMidPools const mid = { b->mid.get() };
+    LhMidPsy *const psy = b->dc.front_psy() ? b->midpsy.get() : nullptr;    /* (as large as the frames' pool: batch_mid_reserve) */
     if (split && !p.window && !b->ev_part[0]) {
         if (b->ev_part[0].create() != hipSuccess || b->ev_part[1].create() != hipSuccess)
             return set_err("hipEventCreate", hipGetLastError());
@@ -531,12 +538,12 @@ batch_launch(lamehip_batch * b, const int16_t * pcm, const float *pcmf, const Lh
             hipEvent_t between[2] = { b->ev_win[3 * (size_t) k + 1], b->ev_win[3 * (size_t) k + 2] };
             HIPCHK(hipEventRecord(b->ev_win[3 * (size_t) k], b->stream));
             rc = b->dc.launch_split(pcm, pcmf, b->d_wdesc.get() + (size_t) k * (size_t) b->B, b->d_state.get(), b->d_out.get(), bytes,
-                                    b->B, left < p.window ? left : p.window, mid, stream, between);
+                                    b->B, left < p.window ? left : p.window, mid, psy, stream, between);
         }
     }
     else if (split) {
         hipEvent_t between[2] = { b->ev_part[0], b->ev_part[1] };
-        rc = b->dc.launch_split(pcm, pcmf, descs, b->d_state.get(), b->d_out.get(), bytes, b->B, p.max_frames, mid, stream, between);
+        rc = b->dc.launch_split(pcm, pcmf, descs, b->d_state.get(), b->d_out.get(), bytes, b->B, p.max_frames, mid, psy, stream, between);
     }
     else
         rc = b->dc.launch(pcm, pcmf, descs, b->d_state.get(), b->d_out.get(), bytes, b->B, stream);

@@ -24,10 +24,12 @@
 #ifndef LH_DEVFN
 #ifdef LH_EMU
 #define LH_DEVFN static inline
+#define LH_DEVMEM inline         /* (a member function) */
 #define LH_STAGEFN static
 #define LH_DEVCONST static const
 #else
 #define LH_DEVFN __device__ __forceinline__
+#define LH_DEVMEM __device__ __forceinline__
 /* stage-level functions are NOT inlined: one giant kernel body made the register
  * allocator spill thousands of dwords; per-stage allocation keeps the kernel at
  * two waves per SIMD */

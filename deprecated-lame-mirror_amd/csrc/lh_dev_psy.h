@@ -7,150 +7,28 @@
 
 #include "lh_dev_psy_core.h"
 
-/* reference psymodel.c:1326-1388; one lane per partition, eb/thr are [4][64] in LDS */
-LH_DEVFN void
-lh_ms_thresholds(const LhCtx & c, const float *eb, float *thr, const float *cb_mld,
-                 const float *ath_cb, float athlower, float msfix, int n)
-{
-    int const b = c.lane;
-    if (b < n) {
-        float const msfix2 = msfix * 2.f;
-        float   rside, rmid;
-        float const ebM = eb[2 * 64 + b];
-        float const ebS = eb[3 * 64 + b];
-        float const thmL = thr[0 * 64 + b];
-        float const thmR = thr[1 * 64 + b];
-        float   thmM = thr[2 * 64 + b];
-        float   thmS = thr[3 * 64 + b];
-        if (thmL <= 1.58f * thmR && thmR <= 1.58f * thmL) {
-            float const mld_m = cb_mld[b] * ebS;
-            float const mld_s = cb_mld[b] * ebM;
-            float const tmp_m = __builtin_fminf(thmS, mld_m);
-            float const tmp_s = __builtin_fminf(thmM, mld_s);
-            rmid = __builtin_fmaxf(thmM, tmp_m);
-            rside = __builtin_fmaxf(thmS, tmp_s);
-        }
-        else {
-            rmid = thmM;
-            rside = thmS;
-        }
-        if (msfix > 0.f) {
-            float   thmLR, thmMS;
-            float const ath = ath_cb[b] * athlower;
-            float const tmp_l = __builtin_fmaxf(thmL, ath);
-            float const tmp_r = __builtin_fmaxf(thmR, ath);
-            thmLR = __builtin_fminf(tmp_l, tmp_r);
-            thmM = __builtin_fmaxf(rmid, ath);
-            thmS = __builtin_fmaxf(rside, ath);
-            thmMS = thmM + thmS;
-            if (thmMS > 0.f && (thmLR * msfix2) < thmMS) {
-                float const f = thmLR * msfix2 / thmMS;
-                thmM *= f;
-                thmS *= f;
-            }
-            rmid = __builtin_fminf(thmM, rmid);
-            rside = __builtin_fminf(thmS, rside);
-        }
-        if (rmid > ebM)
-            rmid = ebM;
-        if (rside > ebS)
-            rside = ebS;
-        thr[2 * 64 + b] = rmid;
-        thr[3 * 64 + b] = rside;
-    }
-}
-
 #ifdef LH_SPLIT
-/* The encode kernel of the split pipeline (lh_kernels.hip with -DLH_SPLIT): the analysis kernels (lh_analysis.hip) have
- * done everything of a granule's masking that depends on the PCM alone -- lh_compute_masking < NC, 1 > left the partition
- * energies, the spread energies x weight and the caps in HBM (LhMidMask) --, and what is left are the recurrences: the
- * pre-echo clamp against the two previous long calls, the cap, and the masking adjustment the last frame's loop left
- * (reference psymodel.c:1208-1262 / :1100-1131).  One lane per partition, straight from HBM into registers. */
-struct LhTailChan {
-    int     chn;
-    const LhMidMask *raw;
-    float  *eb, *thr;           /* partition energies / thresholds out (LDS, 64 each) */
-    float  *nb1, *nb2;
+/* where stages 6 - 8 (lh_psy_stage_*, lh_dev_psy_core.h) find things in the encode kernel's LDS: the psy scratch and ring slot `now' */
+struct LhPsyAt {
+    int     now;
+    LH_DEVMEM float *eb(int chn) const { return &lh_lds.u.psy.eb[chn * 64]; }
+    LH_DEVMEM float *thr(int chn) const { return &lh_lds.u.psy.thr[chn * 64]; }
+    LH_DEVMEM float *en(int chn) const { return &lh_lds.psy_en[now][chn][0]; }
+    LH_DEVMEM float *thm(int chn) const { return &lh_lds.psy_thm[now][chn][0]; }
+    LH_DEVMEM int uselong(int ch) const { return lh_lds.uselongblock[ch]; }
 };
 
-template < int NC > LH_DEVFN void
-lh_masking_tail(const LhCtx & c, int is_long, const LhTailChan (&ch)[NC])
-{
-    LhPsyBand const *gd = is_long ? &c.T->psy_l : &c.T->psy_s;
-    int const b = c.lane;
-    int const np = gd->npart;
-    int const on = b < np;
-    float const t_mlow = gd->masking_lower[on ? b : 0];
-    float   ebb[NC], ecb[NC], cap[NC], th[NC];
-#pragma unroll
-    for (int q = 0; q < NC; q++) {
-        ebb[q] = ch[q].raw->v[0][b];
-        ecb[q] = ch[q].raw->v[1][b];
-        cap[q] = ch[q].raw->v[2][b];
-        th[q] = 0;
-    }
-    if (on) {
-        float const masking_lower = t_mlow * lh_lds.ss.masking_lower;
-#pragma unroll
-        for (int q = 0; q < NC; q++) {
-            float   x, e = ecb[q], t;
-            if (is_long) {
-                int const bt_old = lh_lds.ss.blocktype_old[ch[q].chn & 1];
-                float const n1v = *ch[q].nb1, n2v = *ch[q].nb2;
-                if (bt_old == LH_SHORT_TYPE) {
-                    float const ecb_limit = LH_RPELEV * n1v;
-                    if (ecb_limit > 0)
-                        t = __builtin_fminf(e, ecb_limit);
-                    else {
-                        float const alt = (float) (ebb[q] * LH_PREECHO_ATT2);
-                        t = __builtin_fminf(e, alt);
-                    }
-                }
-                else {
-                    float   lim2 = LH_RPELEV2 * n2v;
-                    float   lim1 = LH_RPELEV * n1v;
-                    float   lim;
-                    if (lim2 <= 0)
-                        lim2 = e;
-                    if (lim1 <= 0)
-                        lim1 = e;
-                    if (bt_old == LH_NORM_TYPE)
-                        lim = __builtin_fminf(lim1, lim2);
-                    else
-                        lim = lim1;
-                    t = __builtin_fminf(e, lim);
-                }
-                *ch[q].nb2 = n1v;
-                *ch[q].nb1 = e;
-            }
-            else
-                t = e;
-            x = cap[q];
-            if (t > x)
-                t = x;
-            if (masking_lower > 1)
-                t *= masking_lower;
-            if (t > ebb[q])
-                t = ebb[q];
-            if (masking_lower < 1)
-                t *= masking_lower;
-            th[q] = t;
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < NC; q++) {
-        ch[q].eb[b] = ebb[q];   /* 0 above the last partition */
-        ch[q].thr[b] = th[q];
-    }
-    LH_WAVE_SYNC_MEM();
-}
+/* (front: the launch runs behind the front masking kernels, lh_psy_finish.hip -- the same for every frame of a launch) */
+#define LH_PSY_FRONT_PARAM , int front
+#else
+#define LH_PSY_FRONT_PARAM
 #endif
 
 /* ------------------------------------------------------------------ */
 /* One granule of the psycho-acoustic model for the whole workgroup     */
 /* (reference L3psycho_anal_vbr, psymodel.c:1397-1597).                 */
 LH_STAGEFN LhPsyCarry
-lh_psy_granule(int gr, LhPsyCarry nb)
+lh_psy_granule(int gr, LhPsyCarry nb LH_PSY_FRONT_PARAM)
 {
     LhCtx const c = lh_ctx_load();
     LhLds & L = lh_lds;
@@ -455,21 +333,25 @@ lh_psy_granule(int gr, LhPsyCarry nb)
     LH_SYNC_WG_LDS();
 #endif                          /* !LH_SPLIT */
     LH_PA(32, t_psy0);
-    LQ_MARK("ps_mask");
-    /* (6) masking thresholds, long blocks: the wave's one or two pseudo-channels together */
 #ifdef LH_SPLIT
-    if (n_chn_psy == 4) {
-        LhTailChan const two[2] = {
-            {w, &mlong->m[gr][w], &P.eb[w * 64], &P.thr[w * 64], &nb.n1[0], &nb.n2[0]},
-            {w + 2, &mlong->m[gr][w + 2], &P.eb[(w + 2) * 64], &P.thr[(w + 2) * 64], &nb.n1[1], &nb.n2[1]}
-        };
-        lh_masking_tail < 2 > (c, 1, two);
-    }
-    else if (w < n_chn_psy) {
-        LhTailChan const one[1] = { {w, &mlong->m[gr][w], &P.eb[w * 64], &P.thr[w * 64], &nb.n1[0], &nb.n2[0]} };
-        lh_masking_tail < 1 > (c, 1, one);
+    /* (6) - (8): the stages themselves are in lh_dev_psy_core.h.  In a launch that has the front masking kernels' records
+     * (lh_psy_finish.hip) they have run already: this granule's band energies / thresholds are in ring slot `now' since the
+     * top of the frame (lh_encode_frame), and the partition energies of the clamp (nb) are taken from the launch's last
+     * records when it ends (lh_encode_stream). */
+    if (!lh_uni_i(front)) {
+        LhPsyAt const at = { now };
+        LQ_MARK("ps_mask");
+        lh_psy_stage_mask(c, gr, n_chn_psy, mlong, nb, lh_lds.ss.ath_adjust_factor, at);
+        LH_PA(33, t_psy0);
+        LQ_MARK("ps_p2sfb");
+        lh_psy_stage_bands(c, n_chn_psy, at);
+        LH_PA(34, t_psy0);
+        LQ_MARK("ps_short");
+        lh_psy_stage_short(c, gr, n_chn_psy, mshort, nb, lh_lds.ss.ath_adjust_factor, at);
     }
 #else
+    LQ_MARK("ps_mask");
+    /* (6) masking thresholds, long blocks: the wave's one or two pseudo-channels together */
     if (n_chn_psy == 4) {
         LhMaskChan const two[2] = {
             {w, P.b.energy[w], &P.eb[w * 64], &P.thr[w * 64], &nb.n1[0], &nb.n2[0]},
@@ -481,7 +363,6 @@ lh_psy_granule(int gr, LhPsyCarry nb)
         LhMaskChan const one[1] = { {w, P.b.energy[w], &P.eb[w * 64], &P.thr[w * 64], &nb.n1[0], &nb.n2[0]} };
         lh_compute_masking < 1 > (c, 1, one, stg_s3);
     }
-#endif
     LH_SYNC_WG_LDS();
     if (cfg->mode == LH_MODE_JOINT_STEREO && (L.uselongblock[0] + L.uselongblock[1]) == 2) {
         float const ath_factor =
@@ -513,30 +394,14 @@ lh_psy_granule(int gr, LhPsyCarry nb)
     /* (nothing of it runs when both channels keep long blocks -- the usual granule: the values the
      * short transforms would replace are the long->short estimates of stage 7) */
     int const any_short = lh_uni_i(!(L.uselongblock[0] && L.uselongblock[1]));
-#ifndef LH_SPLIT
     if (any_short) {
         if (!L.uselongblock[w])
             lh_fft_short(c, w, bufbase, &P.wsamp[w][0]);
         LH_SYNC_WG_LDS();
     }
-#endif
     for (int sblock = 0; any_short && sblock < 3; sblock++) {
         if (w < n_chn_psy && !L.uselongblock[w]) {
             /* (wave w's pseudo-channels w and w + 2 share uselongblock[w]) */
-#ifdef LH_SPLIT
-            if (n_chn_psy == 4) {
-                LhTailChan const two[2] = {
-                    {w, &mshort->m[gr][sblock][w], &P.eb[w * 64], &P.thr[w * 64], &nb.n1[0], &nb.n2[0]},
-                    {w + 2, &mshort->m[gr][sblock][w + 2], &P.eb[(w + 2) * 64], &P.thr[(w + 2) * 64], &nb.n1[1], &nb.n2[1]}
-                };
-                lh_masking_tail < 2 > (c, 0, two);
-            }
-            else {
-                LhTailChan const one[1] = { {w, &mshort->m[gr][sblock][w], &P.eb[w * 64], &P.thr[w * 64], &nb.n1[0], &nb.n2[0]} };
-                lh_masking_tail < 1 > (c, 0, one);
-            }
-        }
-#else
             int const both = (n_chn_psy == 4);
             if (both)
                 lh_fft_energy_pair(c, w, &P.wsamp[0][sblock * LH_BLKSIZE_S], &P.wsamp[1][sblock * LH_BLKSIZE_S],
@@ -557,7 +422,6 @@ lh_psy_granule(int gr, LhPsyCarry nb)
                 lh_compute_masking < 1 > (c, 0, one, T->psy_s.s3);
             }
         }
-#endif
         LH_SYNC_WG_LDS();
         if (cfg->mode == LH_MODE_JOINT_STEREO && (L.uselongblock[0] + L.uselongblock[1]) == 0) {
             float const ath_factor =
@@ -576,6 +440,7 @@ lh_psy_granule(int gr, LhPsyCarry nb)
         }
         LH_SYNC_WG_LDS();
     }
+#endif
     LH_PA(35, t_psy0);
     LQ_MARK("ps_preecho");
     /* (9) short block pre-echo control (reference psymodel.c:1502-1553): one lane per (chn, sb) */

@@ -847,4 +847,273 @@ lh_compute_masking(const LhCtx & c, int is_long, const LhMaskChan (&ch)[NC], con
     LH_PA(17, t_mk);
 }
 
+/* reference psymodel.c:1326-1388; one lane per partition, eb/thr are [4][64] in LDS */
+LH_DEVFN void
+lh_ms_thresholds(const LhCtx & c, const float *eb, float *thr, const float *cb_mld,
+                 const float *ath_cb, float athlower, float msfix, int n)
+{
+    int const b = c.lane;
+    if (b < n) {
+        float const msfix2 = msfix * 2.f;
+        float   rside, rmid;
+        float const ebM = eb[2 * 64 + b];
+        float const ebS = eb[3 * 64 + b];
+        float const thmL = thr[0 * 64 + b];
+        float const thmR = thr[1 * 64 + b];
+        float   thmM = thr[2 * 64 + b];
+        float   thmS = thr[3 * 64 + b];
+        if (thmL <= 1.58f * thmR && thmR <= 1.58f * thmL) {
+            float const mld_m = cb_mld[b] * ebS;
+            float const mld_s = cb_mld[b] * ebM;
+            float const tmp_m = __builtin_fminf(thmS, mld_m);
+            float const tmp_s = __builtin_fminf(thmM, mld_s);
+            rmid = __builtin_fmaxf(thmM, tmp_m);
+            rside = __builtin_fmaxf(thmS, tmp_s);
+        }
+        else {
+            rmid = thmM;
+            rside = thmS;
+        }
+        if (msfix > 0.f) {
+            float   thmLR, thmMS;
+            float const ath = ath_cb[b] * athlower;
+            float const tmp_l = __builtin_fmaxf(thmL, ath);
+            float const tmp_r = __builtin_fmaxf(thmR, ath);
+            thmLR = __builtin_fminf(tmp_l, tmp_r);
+            thmM = __builtin_fmaxf(rmid, ath);
+            thmS = __builtin_fmaxf(rside, ath);
+            thmMS = thmM + thmS;
+            if (thmMS > 0.f && (thmLR * msfix2) < thmMS) {
+                float const f = thmLR * msfix2 / thmMS;
+                thmM *= f;
+                thmS *= f;
+            }
+            rmid = __builtin_fminf(thmM, rmid);
+            rside = __builtin_fminf(thmS, rside);
+        }
+        if (rmid > ebM)
+            rmid = ebM;
+        if (rside > ebS)
+            rside = ebS;
+        thr[2 * 64 + b] = rmid;
+        thr[3 * 64 + b] = rside;
+    }
+}
+
+#if defined(LH_SPLIT) || defined(LH_PSY_FINISH)
+/* The encode kernel of the split pipeline (lh_kernels.hip with -DLH_SPLIT): the analysis kernels (lh_analysis.hip) have
+ * done everything of a granule's masking that depends on the PCM alone -- lh_compute_masking < NC, 1 > left the partition
+ * energies, the spread energies x weight and the caps in HBM (LhMidMask) --, and what is left are the recurrences: the
+ * pre-echo clamp against the two previous long calls, the cap, and the masking adjustment the last frame's loop left
+ * (reference psymodel.c:1208-1262 / :1100-1131).  One lane per partition, straight from HBM into registers. */
+struct LhTailChan {
+    int     chn;
+    const LhMidMask *raw;
+    float  *eb, *thr;           /* partition energies / thresholds out (LDS, 64 each) */
+    float  *nb1, *nb2;
+};
+
+template < int NC > LH_DEVFN void
+lh_masking_tail(const LhCtx & c, int is_long, const LhTailChan (&ch)[NC])
+{
+    LhPsyBand const *gd = is_long ? &c.T->psy_l : &c.T->psy_s;
+    int const b = c.lane;
+    int const np = gd->npart;
+    int const on = b < np;
+    float const t_mlow = gd->masking_lower[on ? b : 0];
+    float   ebb[NC], ecb[NC], cap[NC], th[NC];
+#pragma unroll
+    for (int q = 0; q < NC; q++) {
+        ebb[q] = ch[q].raw->v[0][b];
+        ecb[q] = ch[q].raw->v[1][b];
+        cap[q] = ch[q].raw->v[2][b];
+        th[q] = 0;
+    }
+    if (on) {
+        float const masking_lower = t_mlow * lh_lds.ss.masking_lower;
+#pragma unroll
+        for (int q = 0; q < NC; q++) {
+            float   x, e = ecb[q], t;
+            if (is_long) {
+                int const bt_old = lh_lds.ss.blocktype_old[ch[q].chn & 1];
+                float const n1v = *ch[q].nb1, n2v = *ch[q].nb2;
+                if (bt_old == LH_SHORT_TYPE) {
+                    float const ecb_limit = LH_RPELEV * n1v;
+                    if (ecb_limit > 0)
+                        t = __builtin_fminf(e, ecb_limit);
+                    else {
+                        float const alt = (float) (ebb[q] * LH_PREECHO_ATT2);
+                        t = __builtin_fminf(e, alt);
+                    }
+                }
+                else {
+                    float   lim2 = LH_RPELEV2 * n2v;
+                    float   lim1 = LH_RPELEV * n1v;
+                    float   lim;
+                    if (lim2 <= 0)
+                        lim2 = e;
+                    if (lim1 <= 0)
+                        lim1 = e;
+                    if (bt_old == LH_NORM_TYPE)
+                        lim = __builtin_fminf(lim1, lim2);
+                    else
+                        lim = lim1;
+                    t = __builtin_fminf(e, lim);
+                }
+                *ch[q].nb2 = n1v;
+                *ch[q].nb1 = e;
+            }
+            else
+                t = e;
+            x = cap[q];
+            if (t > x)
+                t = x;
+            if (masking_lower > 1)
+                t *= masking_lower;
+            if (t > ebb[q])
+                t = ebb[q];
+            if (masking_lower < 1)
+                t *= masking_lower;
+            th[q] = t;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < NC; q++) {
+        ch[q].eb[b] = ebb[q];   /* 0 above the last partition */
+        ch[q].thr[b] = th[q];
+    }
+    LH_WAVE_SYNC_MEM();
+}
+
+/* Stages 6 - 8 of a granule's model in the split pipeline (lh_psy_granule), whole workgroup, wave w = pseudo-channels w and
+ * w + 2.  Two callers: the encode kernel (lh_dev_psy.h) and, for CBR / ABR launches, lh_psy_mask_kernel (lh_psy_finish.hip),
+ * which runs them for all granules of a launch at once.  W says where the caller keeps things in ITS LDS image -- eb(chn) /
+ * thr(chn): the partition arrays, en(chn) / thm(chn): the channel's band image (22 long values, 13 x 3 short ones),
+ * uselong(ch) --; small inline functions, so that every access keeps its constant LDS address. */
+
+/* (6) masking thresholds of the long blocks under the recurrences, then the mid/side thresholds (reference psymodel.c:1326-1388) */
+template < class W > LH_DEVFN void
+lh_psy_stage_mask(const LhCtx & c, int gr, int n_chn_psy, const LhMidLong * mlong, LhPsyCarry & nb, float ath_adjust_factor, W at)
+{
+    int const w = c.wave;
+    if (n_chn_psy == 4) {
+        LhTailChan const two[2] = {
+            {w, &mlong->m[gr][w], at.eb(w), at.thr(w), &nb.n1[0], &nb.n2[0]},
+            {w + 2, &mlong->m[gr][w + 2], at.eb(w + 2), at.thr(w + 2), &nb.n1[1], &nb.n2[1]}
+        };
+        lh_masking_tail < 2 > (c, 1, two);
+    }
+    else if (w < n_chn_psy) {
+        LhTailChan const one[1] = { {w, &mlong->m[gr][w], at.eb(w), at.thr(w), &nb.n1[0], &nb.n2[0]} };
+        lh_masking_tail < 1 > (c, 1, one);
+    }
+    LH_SYNC_WG_LDS();
+    if (c.cfg->mode == LH_MODE_JOINT_STEREO && (at.uselong(0) + at.uselong(1)) == 2) {
+        float const ath_factor = (c.cfg->msfix > 0.f) ? (c.cfg->ATH_offset_factor * ath_adjust_factor) : 1.f;
+        if (w == 0)
+            lh_ms_thresholds(c, at.eb(0), at.thr(0), c.T->psy_l.mld_cb, c.T->ath_cb_l, ath_factor, c.cfg->msfix, c.T->psy_l.npart);
+    }
+    LH_SYNC_WG_LDS();
+}
+
+/* (7) partitions -> scalefactor bands, long and long->short estimates (reference psymodel.c:411-439): both tables and the
+ * wave's pseudo-channels in one pass */
+template < class W > LH_DEVFN void
+lh_psy_stage_bands(const LhCtx & c, int n_chn_psy, W at)
+{
+    int const w = c.wave;
+    if (n_chn_psy == 4) {
+        LhSfbChan const two[2] = {
+            {at.eb(w), at.thr(w), at.en(w), at.thm(w)},
+            {at.eb(w + 2), at.thr(w + 2), at.en(w + 2), at.thm(w + 2)}
+        };
+        lh_partition2sfb_long < 2 > (c.T, two, c.lane);
+    }
+    else if (w < n_chn_psy) {
+        LhSfbChan const one[1] = { {at.eb(w), at.thr(w), at.en(w), at.thm(w)} };
+        lh_partition2sfb_long < 1 > (c.T, one, c.lane);
+    }
+    LH_SYNC_WG_LDS();
+}
+
+/* (8) short blocks (reference psymodel.c:1470-1500).  Nothing of it runs when both channels keep long blocks -- the usual
+ * granule: the values the short transforms would replace are the long->short estimates of stage 7 */
+template < class W > LH_DEVFN void
+lh_psy_stage_short(const LhCtx & c, int gr, int n_chn_psy, const LhMidShort * mshort, LhPsyCarry & nb, float ath_adjust_factor, W at)
+{
+    int const w = c.wave;
+    int const any_short = lh_uni_i(!(at.uselong(0) && at.uselong(1)));
+    for (int sblock = 0; any_short && sblock < 3; sblock++) {
+        if (w < n_chn_psy && !at.uselong(w)) {
+            /* (wave w's pseudo-channels w and w + 2 share uselongblock[w]) */
+            if (n_chn_psy == 4) {
+                LhTailChan const two[2] = {
+                    {w, &mshort->m[gr][sblock][w], at.eb(w), at.thr(w), &nb.n1[0], &nb.n2[0]},
+                    {w + 2, &mshort->m[gr][sblock][w + 2], at.eb(w + 2), at.thr(w + 2), &nb.n1[1], &nb.n2[1]}
+                };
+                lh_masking_tail < 2 > (c, 0, two);      /* short: nb left alone */
+            }
+            else {
+                LhTailChan const one[1] = { {w, &mshort->m[gr][sblock][w], at.eb(w), at.thr(w), &nb.n1[0], &nb.n2[0]} };
+                lh_masking_tail < 1 > (c, 0, one);
+            }
+        }
+        LH_SYNC_WG_LDS();
+        if (c.cfg->mode == LH_MODE_JOINT_STEREO && (at.uselong(0) + at.uselong(1)) == 0) {
+            float const ath_factor = (c.cfg->msfix > 0.f) ? (c.cfg->ATH_offset_factor * ath_adjust_factor) : 1.f;
+            if (w == 0)
+                lh_ms_thresholds(c, at.eb(0), at.thr(0), c.T->psy_s.mld_cb, c.T->ath_cb_s, ath_factor, c.cfg->msfix, c.T->psy_s.npart);
+        }
+        LH_SYNC_WG_LDS();
+        for (int t = 0; t < 2; t++) {
+            int const chn = w + 2 * t;
+            int const act = chn < n_chn_psy && !at.uselong(chn & 1);
+            int const cc = (chn < n_chn_psy) ? chn : w;
+            lh_partition2sfb_wave(&c.T->psy_s, at.eb(cc), at.thr(cc), at.en(cc) + 22 + sblock, at.thm(cc) + 22 + sblock, 3, -1.0f, 0,
+                                  c.lane, act);
+        }
+        LH_SYNC_WG_LDS();
+    }
+}
+#endif
+
+/* The ATH level follows the loudness of the frame (reference encoder.c:56-137, adjust_ATH; wave-uniform):
+ * `factor' scales the threshold in quiet, `limit' is the floor it may not be raised above on the way
+ * back up.  A loud frame (half the louder granule's loudness, times the sensitivity, above 1/32)
+ * snaps the factor back into [limit, 1]; a quiet one pulls it towards 31.98 x that level + 0.000625 --
+ * from above by 7.5 % of the way per frame, from below at once, within the previous limit. */
+LH_DEVFN void
+lh_adjust_ATH(const LhTables * T, const float loud[2][2], float *factor, float *limit)
+{
+    float const was = *factor, floor_was = *limit;
+    float   level, now, floor_now;
+    if (T->ath_use_adjust == 0) {
+        *factor = 1.0;
+        return;
+    }
+    {
+        float const first = loud[0][0] + loud[0][1], second = loud[1][0] + loud[1][1];
+        /* (MPEG-2 / 2.5: the frame's only granule, reference encoder.c:80-82: loud[1] is passed as loud[0] then) */
+        level = (first > second) ? first : second;
+        level = (float) (level * 0.5);
+        level *= T->aa_sensitivity_p;
+    }
+    if (level > 0.03125) {
+        now = (was >= 1.0) ? 1.0f : (was < floor_was) ? floor_was : was;
+        floor_now = 1.0;
+    }
+    else {
+        float const quiet = (float) (31.98 * level + 0.000625);
+        if (was >= quiet) {
+            float const eased = (float) (was * (quiet * 0.075 + 0.925));
+            now = (eased < quiet) ? quiet : eased;
+        }
+        else
+            now = (floor_was >= quiet) ? quiet : (was < floor_was) ? floor_was : was;
+        floor_now = quiet;
+    }
+    *factor = now;
+    *limit = floor_now;
+}
+
 #endif

@@ -91,9 +91,20 @@ typedef struct LhStreamState {
     float   dbg_pe[2][2];
     int     dbg_targ[2][2];
     int     dbg_mean_bits;
-    int     dbg_pad[3];
+    int     dbg_front_frames;   /* frames whose prologue started from an LhMidPsy record (cumulative since lh_state_init; writer: thread 0) */
+    int     dbg_pad[2];
 #endif
 } LhStreamState;
+
+/* Who writes the psycho-acoustic state when a launch of the split pipeline runs the front masking kernels (lh_psy_finish.hip;
+ * CBR / ABR launches of MPEG-1 streams): the front kernels only READ LhStreamState (nb_l1 / nb_l2 for the launch's first two
+ * granules, loudness_sq_save, ath_adjust_*, blocktype_old and masking_lower for its first frame) and write nothing but
+ * their records.  The encode kernel still writes every field at the end of the launch, as it does without them: en / thm,
+ * tot_ener, last_en_subshort, last_attacks, blocktype_old, ath_adjust_*, pefirbuf, masking_lower and loudness_sq_save from
+ * the values it keeps in LDS (it still runs the ATH adjustment, the short-block pre-echo and the perceptual entropy itself),
+ * nb_l1 / nb_l2 from the unclamped spread energies (LhMidLong.m[gr][chn].v[1]) of the launch's last two granules.  So
+ * whichever kernel takes the stream's next launch -- fused, split with or without the front kernels, a window, a round --
+ * finds the same words. */
 
 /* one stream's work for one launch */
 typedef struct LhStreamDesc {
@@ -151,6 +162,19 @@ typedef struct LhMidShort {
 typedef struct LhMidXr {
     float   xr[2][2][576];      /* [ch][gr] MDCT spectra of L / R (before the mid/side rotation) */
 } LhMidXr;
+
+/* What lh_psy_finish.hip leaves for the encode kernel of a CBR / ABR launch (a pool beside the frames', same index): the band
+ * energies / thresholds of the frame's granules as stages 6 - 8 of the psy model leave them (the masking under the
+ * recurrences, mid/side thresholds, partitions -> bands, short blocks: before the short-block pre-echo control), and in
+ * front of them what lh_ath_scan_kernel found the frame's model to see of the stream's loop-carried words. */
+typedef struct LhMidPsy {
+    float   en[2][4][64];       /* [gr][chn L,R,M,S]: 22 long bands, then 13 x 3 short ones (LhLds.psy_en's layout), 3 words of padding */
+    float   thm[2][4][64];
+    float   ath_factor;         /* ath_adjust_factor before the frame's own adjustment (what its mid/side thresholds use) */
+    float   masking_lower;      /* sv_qnt.masking_lower as the previous frame's loop left it */
+    int8_t  bt_old[2][2];       /* [gr][ch] blocktype_old when the granule's pre-echo clamp runs */
+    int     pad;
+} LhMidPsy;
 
 /* one frame's record: what the pools of a launch are made of */
 typedef struct LhMidFrame {

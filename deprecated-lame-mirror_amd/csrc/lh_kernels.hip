@@ -42,45 +42,6 @@ extern "C" { int lh_emu_poison_lds = 0; }
 #include "lh_dev_quant.h"
 #include "lh_dev_qloop.h"
 
-/* The ATH level follows the loudness of the frame (reference encoder.c:56-137, adjust_ATH; wave-uniform):
- * `factor' scales the threshold in quiet, `limit' is the floor it may not be raised above on the way
- * back up.  A loud frame (half the louder granule's loudness, times the sensitivity, above 1/32)
- * snaps the factor back into [limit, 1]; a quiet one pulls it towards 31.98 x that level + 0.000625 --
- * from above by 7.5 % of the way per frame, from below at once, within the previous limit. */
-LH_DEVFN void
-lh_adjust_ATH(const LhTables * T, const float loud[2][2], float *factor, float *limit)
-{
-    float const was = *factor, floor_was = *limit;
-    float   level, now, floor_now;
-    if (T->ath_use_adjust == 0) {
-        *factor = 1.0;
-        return;
-    }
-    {
-        float const first = loud[0][0] + loud[0][1], second = loud[1][0] + loud[1][1];
-        /* (MPEG-2 / 2.5: the frame's only granule, reference encoder.c:80-82: loud[1] is passed as loud[0] then) */
-        level = (first > second) ? first : second;
-        level = (float) (level * 0.5);
-        level *= T->aa_sensitivity_p;
-    }
-    if (level > 0.03125) {
-        now = (was >= 1.0) ? 1.0f : (was < floor_was) ? floor_was : was;
-        floor_now = 1.0;
-    }
-    else {
-        float const quiet = (float) (31.98 * level + 0.000625);
-        if (was >= quiet) {
-            float const eased = (float) (was * (quiet * 0.075 + 0.925));
-            now = (eased < quiet) ? quiet : eased;
-        }
-        else
-            now = (floor_was >= quiet) ? quiet : (was < floor_was) ? floor_was : was;
-        floor_now = quiet;
-    }
-    *factor = now;
-    *limit = floor_now;
-}
-
 LH_DEVCONST float lh_pe_fir[9] = {
     (float) (-0.0207887 * 5), (float) (-0.0378413 * 5), (float) (-0.0432472 * 5),
     (float) (-0.031183 * 5), (float) (7.79609e-18 * 5), (float) (0.0467745 * 5),
@@ -316,12 +277,20 @@ lh_prio_tick(int me, int left)
 #define LH_PRIO_APPLY(rel, late) do { } while (0)
 #endif
 
+#ifdef LH_SPLIT
+#define LH_PSY_PARAM , const LhMidPsy * pr
+#define LH_PSY_FLAG , lh_uni_i(pr != nullptr)
+#else
+#define LH_PSY_PARAM
+#define LH_PSY_FLAG
+#endif
+
 /* The frame and the stream loop are inlined into the kernel: out of line they saved and restored ~60 registers per
  * frame through scratch memory, 50 KB of HBM traffic per frame at no gain. */
 
 /* one frame of one stream; executed by the whole workgroup */
 LH_DEVFN void
-lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry)
+lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry LH_PSY_PARAM)
 {
     LhLds & L = lh_lds;
     const LhConfig *cfg = c.cfg;
@@ -354,8 +323,10 @@ lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry)
         const LhMidFrame *rec = LH_AS_GLOBAL(const LhMidFrame, L.ctx.mid);
         const lh_f32x4 *sx = (const lh_f32x4 *) rec->xr.xr, *sm = (const lh_f32x4 *) &rec->small;
         lh_f32x4 *dx = (lh_f32x4 *) L.xr, *dm = (lh_f32x4 *) &L.u.psy.mid.small;
-        constexpr int NM = (int) ((sizeof(LhMidSmall) + sizeof(LhMidLong)) / 16);      /* 420 */
         static_assert(__builtin_offsetof(LhMidFrame, lng) == sizeof(LhMidSmall) && sizeof(LhMidSmall) % 16 == 0, "small and lng are one run");
+        /* (behind the front masking kernels -- pr: the frame's LhMidPsy record, else null -- the long-block masking is not
+         * needed: the small record alone, and the band energies / thresholds that came of the masking below) */
+        int const NM = lh_uni_i(pr ? (int) (sizeof(LhMidSmall) / 16) : (int) ((sizeof(LhMidSmall) + sizeof(LhMidLong)) / 16));     /* 36 : 420 */
         lh_f32x4 v[5], m[4];
 #pragma unroll
         for (int u = 0; u < 5; u++)
@@ -363,6 +334,35 @@ lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry)
 #pragma unroll
         for (int u = 0; u < 4; u++)
             m[u] = sm[(tid + LH_NT * u < NM) ? tid + LH_NT * u : NM - 1];
+        if (pr) {
+            /* both granules' band images straight to the ring slots stages 6 - 8 of the psy model would have filled (slot
+             * c + 1 + gr, see LhLds.psy_en: nothing else writes them in such a launch); the rows of the model's channels lie
+             * back to back in the ring, 64 words apart in the record */
+            int const nrow = LH_XMIN_N * ((cfg->mode == LH_MODE_JOINT_STEREO) ? 4 : cfg->channels);
+            int const slot0 = lh_uni_i(L.psy_slot);
+            float   e[2][2], t[2][2];
+            static_assert(4 * LH_XMIN_N <= 2 * LH_NT, "a granule's bands: two per thread");
+#pragma unroll
+            for (int gr = 0; gr < 2; gr++)
+#pragma unroll
+                for (int u = 0; u < 2; u++) {
+                    int const i = (tid + LH_NT * u < nrow) ? tid + LH_NT * u : 0, chn = i / LH_XMIN_N, b = i - chn * LH_XMIN_N;
+                    e[gr][u] = pr->en[gr][chn][b];
+                    t[gr][u] = pr->thm[gr][chn][b];
+                }
+#pragma unroll
+            for (int gr = 0; gr < 2; gr++)
+#pragma unroll
+                for (int u = 0; u < 2; u++)
+                    if (tid + LH_NT * u < nrow) {
+                        (&L.psy_en[(slot0 + 1 + gr) % 3][0][0])[tid + LH_NT * u] = e[gr][u];
+                        (&L.psy_thm[(slot0 + 1 + gr) % 3][0][0])[tid + LH_NT * u] = t[gr][u];
+                    }
+#ifdef LH_DEBUG_DUMP
+            if (tid == 0)
+                st->dbg_front_frames += 1;
+#endif
+        }
 #pragma unroll
         for (int u = 0; u < 5; u++)
             if (tid + LH_NT * u < 576)
@@ -407,7 +407,7 @@ lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry)
     /* ---- stage 1: psycho-acoustic model, two granules ---- */
     LH_PT(t_psy);
     for (int gr = 0; gr < ngr; gr++)
-        carry.nb = lh_psy_granule(gr, carry.nb);
+        carry.nb = lh_psy_granule(gr, carry.nb LH_PSY_FLAG);
     if (ngr == 1) {
         /* the transforms below also run over the window's second granule (thrown away): give it a block type */
         if (tid < 2)
@@ -856,9 +856,12 @@ lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry)
  * suits the new VBR loop, csrc/Makefile; lh_api.cpp launches it for vbr_mt / vbr_mtrh configurations). */
 #ifdef LH_SPLIT
 #define LH_NAME_Q(n) n##_q
-#define LH_MID_PARAM , LhMidPools mid
-#define LH_MID_ARG , mid
+#define LH_MID_PARAM , LhMidPools mid, const LhMidPsy * psy
+#define LH_MID_ARG , mid, psy
+/* (the frame's LhMidPsy record, or null: uniform, handed down in scalar registers) */
+#define LH_PSY_REC(f) , (psy ? LH_AS_GLOBAL(const LhMidPsy, psy + (c.d.out_index + c.d.mid_rel + ((f) - c.d.frame_begin))) : (const LhMidPsy *) nullptr)
 #else
+#define LH_PSY_REC(f)
 #define LH_NAME_Q(n) n
 #define LH_MID_PARAM
 #define LH_MID_ARG
@@ -876,6 +879,7 @@ lh_encode_frame(LhCtx & c, LhFrameOut * fo, LhWaveCarry & carry)
 #define lh_launch_encode LH_NAME(lh_launch_encode)
 #define lh_emu_encode LH_NAME(lh_emu_encode)    /* (lh_emu_encode_q, lh_emu_encode_q_lsf: the split pipeline's) */
 #define lh_emu_encode_bytes LH_NAME(lh_emu_encode_bytes)
+#define lh_emu_encode_psy LH_NAME(lh_emu_encode_psy)
 /* all frames of one stream (the workgroup's whole job) */
 LH_DEVFN void
 lh_encode_stream(const LhConfig * LH_RESTRICT cfg, const LhTables * LH_RESTRICT T, const int16_t * pcm, const float *pcmf,
@@ -983,7 +987,7 @@ lh_encode_stream(const LhConfig * LH_RESTRICT cfg, const LhTables * LH_RESTRICT 
 #ifdef LH_SPLIT
         LH_SYNC_WG();           /* (the fused kernel's first barrier of a frame follows the window's staging) */
 #endif
-        lh_encode_frame(c, &out[c.d.out_index + (f - c.d.frame_begin)], carry);
+        lh_encode_frame(c, &out[c.d.out_index + (f - c.d.frame_begin)], carry LH_PSY_REC(f));
         slot = (slot + ngr) % 3;
     }
     (void) LH_PRIO_TICK(prio_me, 0);
@@ -991,6 +995,20 @@ lh_encode_stream(const LhConfig * LH_RESTRICT cfg, const LhTables * LH_RESTRICT 
         ((uint32_t *) &st->loudness_sq_save[0])[c.tid] = ((const uint32_t *) &L.ss)[c.tid];
     else if (c.tid < LH_SS_WORDS_A + LH_SS_WORDS_B)
         ((uint32_t *) &st->pefirbuf[0])[c.tid - LH_SS_WORDS_A] = ((const uint32_t *) &L.ss)[c.tid];
+#if defined(LH_SPLIT) && !defined(LH_LSF)
+    if (lh_uni_i(psy != nullptr) && c.d.frame_end > c.d.frame_begin) {
+        /* behind the front masking kernels no clamp ran here: what it would have left are the unclamped spread energies of
+         * the launch's last two long calls, the two granules of its last frame (partitions of the model's channels only:
+         * the other lanes keep what the launch found, as the clamp leaves them) */
+        const LhMidLong *ml = &mid.frames[c.d.out_index + c.d.mid_rel + (c.d.frame_end - 1 - c.d.frame_begin)].lng;
+        int const n_chn_psy = (cfg->mode == LH_MODE_JOINT_STEREO) ? 4 : cfg->channels;
+        for (int p = 0; p < 2; p++)
+            if (c.wave + 2 * p < n_chn_psy && c.lane < T->psy_l.npart) {
+                carry.nb.n1[p] = ml->m[1][c.wave + 2 * p].v[1][c.lane];
+                carry.nb.n2[p] = ml->m[0][c.wave + 2 * p].v[1][c.lane];
+            }
+    }
+#endif
     for (int p = 0; p < 2; p++) {
         st->nb_l1[c.wave + 2 * p][c.lane] = carry.nb.n1[p];
         st->nb_l2[c.wave + 2 * p][c.lane] = carry.nb.n2[p];
@@ -1225,7 +1243,22 @@ lh_emu_encode(const LhConfig * cfg, const LhTables * T, const int16_t * pcm, con
     hipemu_dim3 grid = { (unsigned) nstreams, 1, 1 }, block = { LH_BLOCK, 1, 1 };
     LhMidPools const mid = *pools;
     hipemu_run(grid, block,[=] () {
-               lh_encode_kernel(cfg, T, pcm, pcmf, descs, states, out, bytes, nstreams, mid);
+               lh_encode_kernel(cfg, T, pcm, pcmf, descs, states, out, bytes, nstreams, mid, (const LhMidPsy *) 0);
+               }
+    );
+    return 0;
+}
+
+/* (the same behind lh_emu_psy_finish, lh_psy_finish.hip: the encode kernel starts from the LhMidPsy records) */
+extern "C" int
+lh_emu_encode_psy(const LhConfig * cfg, const LhTables * T, const int16_t * pcm, const float *pcmf,
+                  const LhStreamDesc * descs, LhStreamState * states, LhFrameOut * out, uint8_t * bytes, int nstreams,
+                  const LhMidPools * pools, const LhMidPsy * psy)
+{
+    hipemu_dim3 grid = { (unsigned) nstreams, 1, 1 }, block = { LH_BLOCK, 1, 1 };
+    LhMidPools const mid = *pools;
+    hipemu_run(grid, block,[=] () {
+               lh_encode_kernel(cfg, T, pcm, pcmf, descs, states, out, bytes, nstreams, mid, psy);
                }
     );
     return 0;
